@@ -15,6 +15,12 @@ C4).  --pairs-per-gpu P switches to weak scaling (P pairs per rank).
 A step = registering the rank's batch end to end (TOLDI/kNN/normals setup + the ICP loop),
 clouds already resident in HBM.  value = ICP iterations (all ranks) / step wall time.
 
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds
+what takes runs of its own: the same steps one call at a time, a profiled step with the
+per-kernel, phase and roofline figures, the 8-pair shard and the CPU baseline / parity
+record.  --dump-outputs DIR writes the last timed step's per-pair results as DIR/<name>.npy
+(the pairs are seeded: the same arguments give the same inputs in every run).
+
 Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 under torch.distributed.run.
 """
 from __future__ import annotations
@@ -174,7 +180,8 @@ def main():
     ap.add_argument("--pairs-per-gpu", type=int, default=0,
                     help="weak scaling instead: this many pairs per rank (the global batch grows with N)")
     ap.add_argument("--n-az", type=int, default=1975, help="C4 azimuth steps per revolution (~120k pts at 1975)")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="with --full: the oracle on the host cores over a sample of rank 0's pairs, and the parity record")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="collective backend for N > 1 (gloo: ranks may share one GPU, as in the tests)")
     ap.add_argument("--pair-cache", default="", help="directory for the generated pairs (reused by later runs)")
@@ -193,7 +200,16 @@ def main():
                          "flight = 14,416 / 15,207 / 15,409 / 15,336; its 8-pair shard 11,318 / 12,767 / 13,198 / "
                          "13,453")
     ap.add_argument("--secondary", choices=["auto", "off"], default="auto",
-                    help="C4 at N=1: also time one 8-pair shard on this GPU (the per-GPU work of the 8-GPU job)")
+                    help="with --full, C4 at N=1: also time one 8-pair shard on this GPU (the per-GPU work of the "
+                         "8-GPU job)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the same steps one "
+                         "call at a time (single_call), the profiled step behind the per-kernel, phase and roofline "
+                         "figures, the 8-pair shard (--secondary) and the CPU baseline with its parity record "
+                         "(--cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the last timed step's per-pair results, in batch order, as DIR/<name>.npy "
+                         "(float64): T [n, 4, 4], num_iterations, num_pure_se3_iterations, status [n]")
     args = ap.parse_args()
     W = dict(WORKLOADS[args.workload])
     if args.workload == "C2" and args.c2_setup != "easy":
@@ -281,8 +297,8 @@ def main():
     # the timed steps: one C-ABI call each with prebuilt arguments; every step's results and
     # kernel times land in their own buffers and are read after the timed region.  With
     # --in-flight F > 1 the K steps run F at a time on F engine slots of this GPU (own
-    # streams and buffers, one host thread each: PipelinedBatchRunner) -- the value; then the
-    # same K steps one call at a time (single_call), whose isolated kernel and phase times
+    # streams and buffers, one host thread each: PipelinedBatchRunner) -- the value; then (--full)
+    # the same K steps one call at a time (single_call), whose isolated kernel and phase times
     # feed the per-kernel lines and rooflines below.
     if args.in_flight <= 0:
         args.in_flight = in_flight_for(count)
@@ -317,9 +333,10 @@ def main():
         iters += sum(r.num_iterations for r in res)
         last = res
         log(f"rank {rank}: step {s} done ({sum(r.num_iterations for r in res)} iterations, slot {pipe.owner(s)})")
+    # everything from here to the result exchange takes GPU runs of its own: --full only
     single = None
     iso = pipe
-    if args.in_flight > 1:
+    if args.full and args.in_flight > 1:
         iso = se3icp.PipelinedBatchRunner(make_runner, in_flight=1, steps=args.steps)
         el1 = timed(iso.run_steps)
         its1 = sum(sum(r.num_iterations for r in iso.results(s)) for s in range(args.steps))
@@ -341,14 +358,15 @@ def main():
         setup_ms += res[0].time_setup_ms
     # one untimed step with HIP events around every loop stage: the timed steps carry
     # events only around the SE(3) NN grids (each marker costs the stream a few microseconds)
-    se3icp.set_profiling(True, devi)
-    step()
-    kt_detail = se3icp.last_kernel_times(devi)
-    se3icp.set_profiling(False, devi)
-    # (the timed steps carry no SE(3) NN events either, set_nn_events(False): the NN stage
-    # times, the secondary roofline's included, come from this profiled step)
-    for k in ["nn_prep_ms", "nn_r3_ms", "recheck_ms", "trim_ms", "reduce_ms", "nn_se3_ms"]:
-        ktot[k] = kt_detail[k] * args.steps
+    if args.full:
+        se3icp.set_profiling(True, devi)
+        step()
+        kt_detail = se3icp.last_kernel_times(devi)
+        se3icp.set_profiling(False, devi)
+        # (the timed steps carry no SE(3) NN events either, set_nn_events(False): the NN stage
+        # times, the secondary roofline's included, come from this profiled step)
+        for k in ["nn_prep_ms", "nn_r3_ms", "recheck_ms", "trim_ms", "reduce_ms", "nn_se3_ms"]:
+            ktot[k] = kt_detail[k] * args.steps
 
     # ---- cross-rank: max time, summed work, RCCL gather of the per-pair results
     elapsed, loop_s, iters_all, gathered = sharding.exchange_results(
@@ -362,26 +380,6 @@ def main():
         ms_per_step = 1000.0 * elapsed / args.steps
         rot_errs = [rot_err_deg(r.T, g) for r, g in zip(last, gts)]
         tr_errs = [float(np.linalg.norm(r.T[:3, 3] - g[:3, 3])) for r, g in zip(last, gts)]
-        kms = {k: ktot.get(k, 0.0) for k in ["nn_prep_ms", "nn_se3_ms", "nn_r3_ms", "recheck_ms", "trim_ms",
-                                            "reduce_ms", "lrf_ms"]}
-        nq = max(1.0, ktot.get("lrf_queries", 0.0))
-        lrf_work = {"queries_per_step": ktot.get("lrf_queries", 0.0) / args.steps,
-                    "leaves_per_query": round(ktot.get("lrf_leaves", 0.0) / nq, 2),
-                    "bound_updates_per_query": round(ktot.get("lrf_merges", 0.0) / nq, 2),
-                    "box_tests_per_query": round(ktot.get("lrf_box_tests", 0.0) / nq, 2),
-                    "candidates_per_query": round(ktot.get("lrf_candidates", 0.0) / nq, 2),
-                    "exact_kernel_queries_per_step": ktot.get("lrf_fallback", 0.0) / args.steps}
-        wl = args.workload if args.c2_cloud == "downsample" else f"{args.workload}u"
-        roof_nn = nn_roofline(ktot, kms, wl)
-        # (normals, KNN 30, ISR.cpp:643: both clouds for GICP, the targets for pt2pl, none for pt2pt)
-        roof_lrf = lrf_roofline(ktot, kms, args.steps, W["params"]["number_of_nn_for_LRF"], wl,
-                                {"gicp": 30, "pt2pl": 15, "pt2pt": 0}[W["variant"]])
-        roof_red = reduce_roofline(last, pairs, W, kms["reduce_ms"] / args.steps, wl)
-        # the bench line's roofline is the step's dominant kernel by GPU time; the other
-        # named kernel is reported beside it
-        nn_step = roof_nn["avg_launch_ms"] * roof_nn["launches"] / args.steps
-        lrf_step = roof_lrf["avg_launch_ms"]
-        dominant, other = (roof_lrf, roof_nn) if lrf_step >= nn_step else (roof_nn, roof_lrf)
         out = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -411,33 +409,73 @@ def main():
             # each call's own wall time in the timed region (the calls in flight beside it): the
             # latency a caller sees, against ms_per_step's amortized time
             "ms_per_call": round(1000.0 * float(np.mean([pipe.call_seconds(s) for s in range(args.steps)])), 3),
-            "single_call": single,
             "pairs_per_sec": round(total_pairs / elapsed, 4),
-            "loop_iterations_per_sec": round(iters_all / loop_s, 3) if loop_s > 0 else None,
             "iterations_per_pair_mean": round(iters_all / total_pairs, 2),
             "accuracy_vs_gt": {"rot_deg_max": round(max(rot_errs), 4), "trans_m_max": round(max(tr_errs), 4)},
-            "kernel_ms_per_step": {k: round(v / args.steps, 3) for k, v in kms.items()},
-            "lrf_work": lrf_work,
-            "rechecked_queries_per_step": rechecked / args.steps,
-            # NN certificates (k_nn_prep): share of the loop's queries that still needed a search
-            "nn_searched_frac": {"se3": round(ktot.get("se3_searched", 0.0) / max(1.0, ktot.get("se3_queries", 0.0)), 4),
-                                 "r3": round(ktot.get("r3_searched", 0.0) / max(1.0, ktot.get("r3_queries", 0.0)), 4)},
-            "phase_ms_per_step": {"setup": round(setup_ms / args.steps, 3), "loop": round(loop_ms / args.steps, 3)},
-            "roofline": dominant,
-            "roofline_other": other,
-            "roofline_reduce": roof_red,
-            "cpu_baseline": None,
         }
-        if args.workload == "C4" and world == 1 and args.secondary == "auto" and len(pairs) > 8:
-            out["secondary_8_pair_shard_one_gpu"] = bench_shard8(pairs, W, params, dev, devi,
-                                                                 in_flight=in_flight_for(8) if args.in_flight > 1 else 1)
-        if args.cpu_baseline == "auto":
-            # rank 0's own pairs on the node's host (the same host for every rank), after the
-            # timed region; at N > 1 the whole job's value is compared with it
-            out["cpu_baseline"], out["parity_vs_cpu"] = cpu_baseline(pairs, last, W, value, params, devi)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered)
+        if args.full:
+            out.update(detail_figures(args, W, ktot, last, pairs, single, iters_all, loop_s, rechecked, setup_ms,
+                                      loop_ms))
+            if args.workload == "C4" and world == 1 and args.secondary == "auto" and len(pairs) > 8:
+                out["secondary_8_pair_shard_one_gpu"] = bench_shard8(
+                    pairs, W, params, dev, devi, in_flight=in_flight_for(8) if args.in_flight > 1 else 1)
+            if args.cpu_baseline == "auto":
+                # rank 0's own pairs on the node's host (the same host for every rank), after the
+                # timed region; at N > 1 the whole job's value is compared with it
+                out["cpu_baseline"], out["parity_vs_cpu"] = cpu_baseline(pairs, last, W, value, params, devi)
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, records):
+    """--dump-outputs: what the last timed step returned for every pair of the batch (the
+    gathered sharding.PairRecords, in batch order), one float64 array per field."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in records._asdict().items():
+        np.save(os.path.join(d, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+
+
+def detail_figures(args, W, ktot, last, pairs, single, iters_all, loop_s, rechecked, setup_ms, loop_ms):
+    """--full: the line's per-kernel, phase and roofline figures, from the isolated calls'
+    kernel times and counters (ktot, with the profiled step's stage times)."""
+    kms = {k: ktot.get(k, 0.0) for k in ["nn_prep_ms", "nn_se3_ms", "nn_r3_ms", "recheck_ms", "trim_ms",
+                                        "reduce_ms", "lrf_ms"]}
+    nq = max(1.0, ktot.get("lrf_queries", 0.0))
+    lrf_work = {"queries_per_step": ktot.get("lrf_queries", 0.0) / args.steps,
+                "leaves_per_query": round(ktot.get("lrf_leaves", 0.0) / nq, 2),
+                "bound_updates_per_query": round(ktot.get("lrf_merges", 0.0) / nq, 2),
+                "box_tests_per_query": round(ktot.get("lrf_box_tests", 0.0) / nq, 2),
+                "candidates_per_query": round(ktot.get("lrf_candidates", 0.0) / nq, 2),
+                "exact_kernel_queries_per_step": ktot.get("lrf_fallback", 0.0) / args.steps}
+    wl = args.workload if args.c2_cloud == "downsample" else f"{args.workload}u"
+    roof_nn = nn_roofline(ktot, kms, wl)
+    # (normals, KNN 30, ISR.cpp:643: both clouds for GICP, the targets for pt2pl, none for pt2pt)
+    roof_lrf = lrf_roofline(ktot, kms, args.steps, W["params"]["number_of_nn_for_LRF"], wl,
+                            {"gicp": 30, "pt2pl": 15, "pt2pt": 0}[W["variant"]])
+    roof_red = reduce_roofline(last, pairs, W, kms["reduce_ms"] / args.steps, wl)
+    # the bench line's roofline is the step's dominant kernel by GPU time; the other
+    # named kernel is reported beside it
+    nn_step = roof_nn["avg_launch_ms"] * roof_nn["launches"] / args.steps
+    lrf_step = roof_lrf["avg_launch_ms"]
+    dominant, other = (roof_lrf, roof_nn) if lrf_step >= nn_step else (roof_nn, roof_lrf)
+    return {
+        "single_call": single,
+        "loop_iterations_per_sec": round(iters_all / loop_s, 3) if loop_s > 0 else None,
+        "kernel_ms_per_step": {k: round(v / args.steps, 3) for k, v in kms.items()},
+        "lrf_work": lrf_work,
+        "rechecked_queries_per_step": rechecked / args.steps,
+        # NN certificates (k_nn_prep): share of the loop's queries that still needed a search
+        "nn_searched_frac": {"se3": round(ktot.get("se3_searched", 0.0) / max(1.0, ktot.get("se3_queries", 0.0)), 4),
+                             "r3": round(ktot.get("r3_searched", 0.0) / max(1.0, ktot.get("r3_queries", 0.0)), 4)},
+        "phase_ms_per_step": {"setup": round(setup_ms / args.steps, 3), "loop": round(loop_ms / args.steps, 3)},
+        "roofline": dominant,
+        "roofline_other": other,
+        "roofline_reduce": roof_red,
+        "cpu_baseline": None,
+    }
 
 
 def nn_roofline(ktot, kms, wl):

@@ -20,8 +20,14 @@ Everything is numpy with an explicit ``numpy.random.Generator(PCG64(seed))``.
 from __future__ import annotations
 
 import os
+import threading
 
 import numpy as np
+
+# numpy's matrix product goes to the BLAS, and concurrent BLAS calls from the ray-casting
+# threads of kitti_like_sequence have returned wrong rows (a few rays of a scan among the
+# first ones cast, differently in every process): the threads take this lock around it
+_BLAS_LOCK = threading.Lock()
 
 
 def rot_3d(roll: float, pitch: float, yaw: float) -> np.ndarray:
@@ -154,7 +160,8 @@ def kitti_like_sequence(n_scans: int, seed: int = 4, n_az: int = 1975, n_beams: 
         az = np.linspace(0, 2 * np.pi, n_az, endpoint=False) + srng.uniform(0, 2 * np.pi / n_az)
         E, A = np.meshgrid(elev + srng.normal(0, 0.0005, n_beams), az, indexing="ij")
         d = np.stack([np.cos(E) * np.cos(A), np.cos(E) * np.sin(A), np.sin(E)], axis=-1).reshape(-1, 3)
-        dw = d @ Rw.T
+        with _BLAS_LOCK:
+            dw = d @ Rw.T
         ts = []
         for c0 in range(0, d.shape[0], 16384):
             ts.append(sc.cast(pk, dw[c0:c0 + 16384], max_range))

@@ -76,10 +76,14 @@ _torch_gpu_ready = False
 
 
 def pytest_runtest_setup(item):
-    """GPU tests: bring up torch's HIP context before libse3icp's first HIP call, as
-    bench.py does (torch only plumbs device buffers for the tests that need them)."""
+    """Bring up torch's HIP context before libse3icp's first HIP call, as bench.py does
+    (torch only plumbs device buffers for the tests that need them).  Before the first test
+    of any kind, not the first GPU one: the CPU tests reach libse3icp's HIP runtime too
+    (se3icp.device_count()), and when the whole suite runs in one process on a GPU machine
+    torch, whose wheel carries a HIP runtime of its own, finds no device once that one was
+    first."""
     global _torch_gpu_ready
-    if _torch_gpu_ready or item.get_closest_marker("gpu") is None:
+    if _torch_gpu_ready:
         return
     _torch_gpu_ready = True
     try:

@@ -122,3 +122,13 @@ def test_synthetic_generators_are_seeded():
     np.testing.assert_array_equal(a[1], b[1])
     f, _ = datasets.rgbd_room_sequence(2, seed=3, stride=16)
     assert (f[0][:, 2] >= 0.39).all() and (f[0][:, 2] <= 4.1).all()
+
+
+def test_kitti_scans_do_not_depend_on_the_casting_threads():
+    """The C4 scans at the benchmark's size (~120k points, where the BLAS runs threaded): the
+    first eight, cast by eight threads at once, are bitwise those of one thread."""
+    from se3icp import datasets
+    ref, _ = datasets.kitti_like_sequence(9, seed=4, scan_indices=range(8), workers=1)
+    got, _ = datasets.kitti_like_sequence(9, seed=4, scan_indices=range(8), workers=8)
+    for k in range(8):
+        np.testing.assert_array_equal(got[k], ref[k])

@@ -28,9 +28,22 @@ def test_two_rank_bench_equals_one_rank(tmp_path):
     one = tmp_path / "one.npy"
     two = tmp_path / "two.npy"
     env = dict(os.environ)
+    dump = tmp_path / "outputs"
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-poses",
-                         str(one)] + common, capture_output=True, text=True, timeout=300, env=env)
+                         str(one), "--dump-outputs", str(dump)] + common, capture_output=True, text=True,
+                        timeout=300, env=env)
     assert r1.returncode == 0, r1.stderr[-3000:]
+    import json
+    d1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
+    # a plain run: the headline fields only, nothing that takes a run of its own (--full)
+    assert d1["steps"] == 1 and d1["ms_per_step"] > 0 and d1["value"] > 0
+    assert not {"single_call", "roofline", "kernel_ms_per_step", "cpu_baseline"} & set(d1)
+    # --dump-outputs: the last timed step's per-pair results, float64, in batch order
+    outs = {n: np.load(dump / f"{n}.npy") for n in ("T", "num_iterations", "num_pure_se3_iterations", "status")}
+    assert all(v.dtype == np.float64 for v in outs.values())
+    assert np.array_equal(outs["T"], np.load(one))
+    assert outs["num_iterations"].shape == (7,) and (outs["num_iterations"] > 0).all()
+    assert (outs["status"] == 0).all()
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                          "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
                          "--gpus", "2", "--backend", "gloo", "--dump-poses", str(two)] + common,
@@ -52,9 +65,14 @@ def test_two_rank_balanced_shards_equal_one_rank(tmp_path):
     gathered poses come back in batch order, bitwise those of one rank."""
     common = ["--steps", "1", "--warmup", "0", "--workload", "C3", "--cpu-baseline", "off", "--global-batch", "7"]
     one, two = tmp_path / "one.npy", tmp_path / "two.npy"
-    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-poses", str(one)] + common,
+    r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dump-poses", str(one)] + common,
                         capture_output=True, text=True, timeout=300)
     assert r1.returncode == 0, r1.stderr[-3000:]
+    import json
+    # --full (the CPU baseline switched off): the figures that take runs of their own are in the line
+    d1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
+    assert d1["single_call"]["ms_per_step"] > 0 and d1["kernel_ms_per_step"]["lrf_ms"] > 0
+    assert {"roofline", "roofline_other", "roofline_reduce", "phase_ms_per_step", "lrf_work"} <= set(d1)
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                          "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
                          "--gpus", "2", "--backend", "gloo", "--shard", "balanced", "--dump-poses", str(two)] + common,

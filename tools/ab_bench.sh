@@ -2,6 +2,7 @@
 # A/B of library builds on one box: tools/ab_bench.sh name1 lib1.so name2 lib2.so ... (alternating twice)
 # prints per run: name, iter/s, ms/step, k_lrf ms, setup ms
 set -e -o pipefail
+AB_ARGS="--full $AB_ARGS"  # (the kernel, phase and LRF figures printed below are --full's)
 mkdir -p gpurun_out
 for rep in 1 2; do
   args=("$@")

@@ -7,6 +7,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}" || exit 1
 : "${AB_VAR:?set AB_VAR to the environment variable to compare}"
 mkdir -p gpurun_out
 VAR=$AB_VAR
+AB_ARGS="--full $AB_ARGS"  # (the kernel and phase figures printed below are --full's)
 for E in ${AB_VALS:-1 0 1 0}; do
   env "$VAR=$E" timeout -k 10 240 python bench.py --steps ${AB_STEPS:-3} --cpu-baseline off $AB_ARGS > gpurun_out/env_$E.json 2> gpurun_out/env_$E.err || exit 1
   python -c "

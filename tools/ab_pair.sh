@@ -5,6 +5,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
 REPS=${AB_REPS:-2}
+AB_ARGS="--full $AB_ARGS"  # (the kernel, phase and LRF figures printed below are --full's)
 for rep in $(seq 1 $REPS); do
   args=("$@")
   while [ ${#args[@]} -gt 0 ]; do

@@ -12,6 +12,8 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
 WA="--workload $W"
 [ "$W" = "C2u" ] && WA="--workload C2 --c2-cloud unique"
+# (--full: the bench line with every figure, and the extra profiled step in the traces)
+WA="--full $WA"
 # (one call at a time: the line's kernel figures come from isolated calls, so the traced
 # kernel averages must too; BENCH_CMD below is the default, calls in flight)
 B="python3 bench.py $WA --steps 3 --warmup 1 --in-flight 1 --cpu-baseline off --secondary off --pair-cache /tmp/se3icp_pairs"

@@ -146,6 +146,37 @@ def test_point_to_plane_step_is_small_rotation_solution():
     assert np.linalg.norm(T - Tsmall) < 2e-3  # one Gauss-Newton step of a linearised problem
 
 
+def test_iteration_cap_quirk_and_overlap_clamp(bunny_unique):
+    """The yardstick's own quirks, pinned where no GPU is needed (tests/test_gpu_params.py
+    relies on both).  The reference tests `num_iterations_ == max_num_iterations_` only in
+    the R3 branch (ISR.cpp:718-727): a run that switches at iteration 10 never equals a cap
+    of 4, passes it by and ends by the MSE criterion.  An estimated_overlap above 1 is
+    clamped to 1 by PCL's rejector: nothing is trimmed."""
+    from se3icp import datasets
+    src, tgt, _ = datasets.bunny_pair(bunny_unique, seed=2, subsample=0.1)
+    base = dict(estimated_overlap=0.7, max_num_se3_iterations=10, mse=1e-5, mse_switch_error=5e-5,
+                number_of_nn_for_LRF=60)
+    free = refcpu.register(src, tgt, refcpu.RUN_SE3_ICP, "pt2pl", refcpu.default_params(**base), trace_iters=160)
+    capped = refcpu.register(src, tgt, refcpu.RUN_SE3_ICP, "pt2pl",
+                             refcpu.default_params(**dict(base, max_num_iterations=4)), trace_iters=160)
+    assert capped["num_pure_se3_iterations"] == 10  # switched by max_num_se3_iterations, past the cap already
+    assert 10 < capped["num_iterations"] < 150
+    assert capped["num_iterations"] == free["num_iterations"]
+    assert np.array_equal(capped["T"], free["T"])
+    n_it = capped["num_iterations"]
+    # ended by |mse - mse_prev| < scaling_factor * mse (ISR.cpp:726), not by a count
+    assert abs(capped["mse"][n_it - 1] - capped["mse"][n_it - 2]) < capped["scaling_factor"] * 1e-5
+    binding = refcpu.register(src, tgt, refcpu.RUN_SE3_ICP, "pt2pl",
+                              refcpu.default_params(**dict(base, max_num_iterations=11)))
+    assert binding["num_iterations"] == 11
+    over = refcpu.register(src, tgt, refcpu.RUN_SE3_ICP, "pt2pt",
+                           refcpu.default_params(**dict(base, estimated_overlap=1.5)), trace_iters=160)
+    full = refcpu.register(src, tgt, refcpu.RUN_SE3_ICP, "pt2pt",
+                           refcpu.default_params(**dict(base, estimated_overlap=1.0)), trace_iters=160)
+    assert (over["n_kept"][:over["num_iterations"]] == src.shape[0]).all()
+    assert over["num_iterations"] == full["num_iterations"] and np.array_equal(over["T"], full["T"])
+
+
 @pytest.mark.parametrize("ratio,n,expected", [(1.0, 1000, 1000), (0.7, 120000, 84000), (0.75, 4167, 3125),
                                               (0.7, 10, 7), (0.0, 5, 0)])
 def test_trim_count_is_pcl_float_floor(ratio, n, expected):

@@ -43,7 +43,9 @@ typedef enum se3icp_status {
     SE3ICP_ERR_NO_DEVICE = -5,        /* no HIP device / kernels not loadable: never a CPU fallback */
     SE3ICP_ERR_HIP = -6,              /* HIP runtime error */
     SE3ICP_ERR_NONFINITE = -7,        /* NaN/Inf in the resulting pose */
-    SE3ICP_ERR_OUT_OF_MEMORY = -8
+    SE3ICP_ERR_OUT_OF_MEMORY = -8,
+    SE3ICP_ERR_INTERNAL = -9          /* a kernel left a result unset or out of range (se3icp_nn: an index
+                                         outside the data cloud); the outputs are not to be used */
 } se3icp_status;
 
 /* Registration methods.  Names match examples/run_registration_method.cpp:19-24

@@ -68,6 +68,7 @@ const char* se3icp_status_string(int status) {
         case SE3ICP_ERR_HIP: return "HIP runtime error";
         case SE3ICP_ERR_NONFINITE: return "non-finite pose";
         case SE3ICP_ERR_OUT_OF_MEMORY: return "out of device memory";
+        case SE3ICP_ERR_INTERNAL: return "internal error: a result left unset or out of range";
         default: return "unknown status";
     }
 }

@@ -1040,8 +1040,16 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
     const int64_t ntot = nq + nd;
     int rc = alloc_points(ntot, 1);
     if (rc) return rc;
-    if (!ensure<PairDev>(d_pairs_, 1) || !ensure<CloudDev>(d_clouds_, 2) || !ensure<int32_t>(d_rechecked_, 1))
+    if (!ensure<PairDev>(d_pairs_, 1) || !ensure<CloudDev>(d_clouds_, 2) || !ensure<CloudSetup>(d_setup_, 2) ||
+        !ensure<int32_t>(d_rechecked_, 1))
         return SE3ICP_ERR_OUT_OF_MEMORY;
+    // k_nn_prep reads the source cloud's alpha for every position: a neutral table of this
+    // call's own (an engine whose first call this is has none; alpha only weighs certificates
+    // of earlier searches, and a one-search run has none)
+    h_setup_.assign(2, CloudSetup{});
+    for (CloudSetup& st : h_setup_) st.alpha = st.beta = st.norm_scale = 1.0;
+    h_setup_[1].is_target = 1;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * 2, hipMemcpyHostToDevice, s));
     h_clouds_.assign(2, CloudDev{});
     h_clouds_[0].off = 0;
     h_clouds_[0].n = (int32_t)nq;
@@ -1107,6 +1115,10 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
     HIPCHK(hipMemcpyAsync(&rech, d_rechecked_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SYNC_STREAM(s);
     if (num_rechecked) *num_rechecked = rech;
+    // every query was searched: an index left unset (-1) or outside the data cloud is a
+    // defect of the build or the search, reported instead of used as a row of `data`
+    for (int64_t i = 0; i < nq; ++i)
+        if (idx[i] < 0 || idx[i] >= nd) return SE3ICP_ERR_INTERNAL;
     if (d2) {
         for (int64_t i = 0; i < nq; ++i) {
             const double* a = query + dim * i;

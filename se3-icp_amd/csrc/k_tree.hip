@@ -776,10 +776,9 @@ __global__ __launch_bounds__(kLevThreads) void k_tree_level(TreeView t, int leve
 #ifndef SE3ICP_TREE_SRC_ORDER_ONLY
 #define SE3ICP_TREE_SRC_ORDER_ONLY 1
 #endif
-constexpr int kLocalMax = 4096;  // power of two
-constexpr int kWaveSortPer = 8;  // sub-nodes of <= 512 points: register sort by one wave
+// (kLocalMax, kWaveSortPer, kLocalPartSubs and the path of a level: tree.hpp)
 constexpr int kLocalThreads = 512;
-static_assert(kLocalMax <= 4096, "wave-sort keys carry the position in 12 bits");
+static_assert(kLocalSubsMax <= 128, "s_best / s_mu / s_sd hold one entry per sub-node");
 
 template <int D>
 // (4 waves per SIMD: two workgroups per CU, <= 128 VGPRs)
@@ -962,8 +961,13 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
             }
         }
         __syncthreads();
-        const int max_sub = (m + nsub - 1) / nsub + 1;  // sub-node sizes differ by <= 1
-        if (max_sub <= 64 * kWaveSortPer) {
+        // the level's path from the exact size of the cloud's largest node of level l
+        // (tree.hpp: block-uniform); more than kLocalPartSubs sub-nodes never reach the
+        // partition by that bound, and the guard keeps its LDS layout safe whatever n is:
+        // the sort stays inside each sub-node's own range of s_val
+        int sort_per = tree_local_sort_per(n, l);
+        if ((int)(sort_per == 0) & (int)(nsub > kLocalPartSubs)) sort_per = kWaveSortPer;
+        if (sort_per != 0) {
             // small sub-nodes: one wave sorts each in registers, in a network of the sub-node's
             // size (128, 256 or 512 keys) over 32-bit keys: the split coordinate quantised to
             // 20 bits over the sub-node's sample mean +- 8 sd | the level-G position (12 bits,
@@ -996,8 +1000,8 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
                     }
                 }
             };
-            if (max_sub <= 128) wave_level(std::integral_constant<int, 2>{});
-            else if (max_sub <= 256) wave_level(std::integral_constant<int, 4>{});
+            if (sort_per == 2) wave_level(std::integral_constant<int, 2>{});
+            else if (sort_per == 4) wave_level(std::integral_constant<int, 4>{});
             else wave_level(std::integral_constant<int, kWaveSortPer>{});
             __syncthreads();
             continue;
@@ -1011,7 +1015,10 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
             constexpr int PER = kLocalMax / kLocalThreads;
             constexpr int kB = 2048;  // bins per pass
             uint32_t* s_h = reinterpret_cast<uint32_t*>(s_key);  // nsub x kB histogram words
-            __shared__ int s_sel[4][4];  // per sub-node: bin / threshold, tie_left, tie_n, cum
+            static_assert(kLocalPartSubs == 4, "cnt / pre / s_sel and the run selects below hold four sub-nodes");
+            static_assert(kLocalPartSubs * kB * sizeof(uint32_t) <= sizeof(s_key), "the histograms stay inside s_key");
+            static_assert(kLocalPartSubs <= kLocalThreads / 64, "find_bin: a wave per sub-node");
+            __shared__ int s_sel[kLocalPartSubs][4];  // per sub-node: bin / threshold, tie_left, tie_n, cum
             __shared__ uint32_t s_scan[kLocalThreads / 64][8];
             for (int x = tid; x < nsub * kB; x += kLocalThreads) s_h[x] = 0u;
             uint32_t q[PER];
@@ -1364,13 +1371,6 @@ __global__ __launch_bounds__(1024) void k_tree_up(TreeView t, int top) {
 }
 
 }  // namespace
-
-int tree_global_levels(int max_n, int L) {
-    int G = 0;  // global levels until every node fits one workgroup's LDS sort (and <= 128 sub-nodes below)
-    while (G < L && (((long long)max_n + (1ll << G) - 1) >> G) > kLocalMax) ++G;
-    if (L - 1 - G > 7) G = L - 8;
-    return G;
-}
 
 namespace {
 struct PartScratch {

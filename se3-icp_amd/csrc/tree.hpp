@@ -69,16 +69,53 @@ __host__ __device__ __forceinline__ size_t tree_tv_ix(size_t ld, int x, int d) {
     return D == 12 ? (size_t)x * 12 + d : (size_t)d * ld + x;
 }
 
+// largest node of a level: node i holds floor(n (i+1) / 2^l) - floor(n i / 2^l) <= ceil(n / 2^l) points
+__host__ __device__ __forceinline__ int tree_max_node(int n, int level) {
+    return (int)(((long long)n + (1ll << level) - 1) >> level);
+}
+
 inline int tree_depth_for(int max_n) {
     int L = 0;
-    while (((long long)max_n + (1ll << L) - 1) >> L > kLeafMax) ++L;
+    while (tree_max_node(max_n, L) > kLeafMax) ++L;
     return L;
+}
+
+// The levels below G are built by one workgroup per level-G node (k_tree_local): nodes of
+// at most kLocalMax points, split level by level into 2^r sub-nodes each.  A level whose
+// sub-nodes fit the register sort of one wave (64 lanes x 2, 4 or kWaveSortPer keys) is
+// sorted; a level of larger sub-nodes goes through the LDS partition, whose histograms and
+// per-sub-node records are laid out for at most kLocalPartSubs of them.
+constexpr int kLocalMax = 4096;     // power of two
+constexpr int kWaveSortPer = 8;     // sub-nodes of <= 512 points: register sort by one wave
+constexpr int kLocalPartSubs = 4;   // sub-nodes per level-G node the LDS partition can hold
+constexpr int kLocalSubsMax = 128;  // sub-nodes per level-G node at the last level (tree_global_levels)
+static_assert((kLocalMax & (kLocalMax - 1)) == 0 && kLocalMax <= 4096, "wave-sort keys carry the position in 12 bits");
+// ceil(ceil(n / 2^G) / 2^r) = ceil(n / 2^(G+r)): with more than kLocalPartSubs sub-nodes
+// (2^r >= 2 kLocalPartSubs) the largest holds <= kLocalMax / (2 kLocalPartSubs) points
+static_assert(kLocalMax / (2 * kLocalPartSubs) <= 64 * kWaveSortPer,
+              "a level of more than kLocalPartSubs sub-nodes must fit the wave sort");
+
+// Keys per lane of the wave sort that orders the sub-nodes of level `level` (2, 4 or
+// kWaveSortPer: networks of 128, 256 and 512 keys), or 0 where the level takes the LDS
+// partition.  From the exact bound, the same for every node of the cloud's level.  (An
+// estimate from the node's own size, ceil(m / nsub) + 1, read 513 for m = 4089 .. 4096 at
+// nsub = 8 and sent eight sub-nodes to the partition.)
+__host__ __device__ __forceinline__ int tree_local_sort_per(int n, int level) {
+    const int mx = tree_max_node(n, level);
+    return mx <= 128 ? 2 : (mx <= 256 ? 4 : (mx <= 64 * kWaveSortPer ? kWaveSortPer : 0));
+}
+
+// global levels until every node fits one workgroup's LDS sort (and <= kLocalSubsMax sub-nodes below)
+inline int tree_global_levels(int max_n, int L) {
+    int G = 0;
+    while (G < L && tree_max_node(max_n, G) > kLocalMax) ++G;
+    if (L - 1 - G > 7) G = L - 8;
+    return G;
 }
 
 // qbuf: [npts] u32 scratch, perm_alt: [npts] the second permutation buffer of the global levels
 int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t* perm_alt, hipStream_t s);
 size_t tree_build_temp_bytes(int npts, int nclouds, int max_n, int L);
-int tree_global_levels(int max_n, int L);
 void tree_prof_report();  // (SE3ICP_PROF builds: k_tree_local's phase timeline, then reset)
 
 }  // namespace se3icp

@@ -21,6 +21,7 @@ ERR_NO_DEVICE = -5
 ERR_HIP = -6
 ERR_NONFINITE = -7
 ERR_OUT_OF_MEMORY = -8
+ERR_INTERNAL = -9
 
 METHODS = ["pt2pt", "pt2pl", "gicp", "se3_pt2pt", "se3_pt2pl", "se3_gicp", "se3_gicp_with_cf",
            "se3_pure_pt2pt", "se3_pure_pt2pl", "se3_pure_gicp"]

@@ -293,7 +293,12 @@ void svd3(const Mat3& A, Mat3& U, double s[3], Mat3& V) {
             u[c] = (1.0 / s[c]) * u[c];
         } else if (c == 2) {
             u[2] = cross(u[0], u[1]);
-        } else {  // rank <= 1: complete an orthonormal basis
+        } else if (c == 0) {  // rank 0 (one kept correspondence: sigma = 0): Eigen's JacobiSVD
+            u[0] = Vec3(1, 0, 0);  // leaves U = V = I, so umeyama's R is the identity
+            u[1] = Vec3(0, 1, 0);
+            u[2] = Vec3(0, 0, 1);
+            break;
+        } else {  // rank 1: complete an orthonormal basis
             Vec3 a = u[0];
             Vec3 e = std::fabs(a.x) < 0.9 ? Vec3(1, 0, 0) : Vec3(0, 1, 0);
             Vec3 t = cross(a, e);

@@ -422,15 +422,22 @@ __device__ __forceinline__ T wsum(T x) {
 // One correspondence's terms (ISR.cpp:689-703, 57-110; MSE ISR.cpp:379-400) added to acc:
 // vs the moved source point, vt the target point, ns0 / nt the source (initial frame) and
 // target normals, w2 the cf weight squared (1 otherwise), dist the stored distance.
-__device__ __forceinline__ void corr_terms(int est, bool cf, const double* T, const double* vs, const double* vt,
-                                           const double* ns0, const double* nt, double w2, double dist, double* acc) {
+// The pt2pt moments are taken about the pair's pivot piv (PairDev::f32_center: the target
+// centroid for run_icp; zero, an exact subtraction, for the normalized methods).  Raw
+// moments of a cloud of spread s at distance |c| from the origin lose eps (|c|/s)^2 in
+// umeyama_from_moments' sigma; pair_close_iteration un-shifts the translation.
+__device__ __forceinline__ void corr_terms(int est, bool cf, const double* T, const double* piv, const double* vs,
+                                           const double* vt, const double* ns0, const double* nt, double w2,
+                                           double dist, double* acc) {
     if (est == EST_PT2PT) {
+        const double ps[3] = {vs[0] - piv[0], vs[1] - piv[1], vs[2] - piv[2]};
+        const double pt[3] = {vt[0] - piv[0], vt[1] - piv[1], vt[2] - piv[2]};
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { acc[a] += vs[a]; acc[3 + a] += vt[a]; }
+        for (int a = 0; a < 3; ++a) { acc[a] += ps[a]; acc[3 + a] += pt[a]; }
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) acc[6 + a * 3 + b] += vt[a] * vs[b];
+            for (int b = 0; b < 3; ++b) acc[6 + a * 3 + b] += pt[a] * ps[b];
         acc[15] += 1.0;
         acc[27] += dist;
         return;
@@ -622,12 +629,13 @@ __global__ __launch_bounds__(kRedThreads) void k_reduce(View v) {
     {
         double T[12];
         load_T(P, T);
+        const double piv[3] = {P->f32_center[0], P->f32_center[1], P->f32_center[2]};
 #pragma unroll
         for (int u = 0; u < kRedPer; ++u) {
             if (!kept[u]) continue;
             double vs[3];
             pose_point(T, xs[u][0], xs[u][1], xs[u][2], vs);
-            corr_terms(est, cf, T, vs, xt[u], n0[u], nt[u], w2[u], (double)dd[u], acc);
+            corr_terms(est, cf, T, piv, vs, xt[u], n0[u], nt[u], w2[u], (double)dd[u], acc);
         }
     }
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -730,11 +738,11 @@ __global__ __launch_bounds__(kFinThreads) void k_reduce_final(View v, const int3
         __builtin_amdgcn_s_waitcnt(0);
         asm volatile("" :: "v"(S.mse_cur), "s"(est_));
         const unsigned long long tfa = __builtin_amdgcn_s_memrealtime();
-        pair_close_iteration(S, est_, tot);
+        pair_close_iteration(S, est_, tot, P->f32_center);
         asm volatile("" :: "v"(S.T.m[0][0]), "v"(S.T.m[2][3]));
         const unsigned long long tfb = __builtin_amdgcn_s_memrealtime();
 #else
-        pair_close_iteration(S, P->est, tot);
+        pair_close_iteration(S, P->est, tot, P->f32_center);
 #endif
         pair_open_iteration(S, *P);
         state[p] = S;

@@ -149,6 +149,9 @@ SE3ICP_HD double det3(const double a[3][3]) {
 // Eigen::umeyama(src, dst, false) (TransformationEstimationPointToPoint, ISR.cpp:692)
 // from the one-pass moments of the kept correspondences:
 //   s[0..2] = sum vs, s[3..5] = sum vt, s[6..14] = sum vt vs^T (row-major), n = count.
+// sigma is invariant under a common shift of vs and vt, and its cancellation costs
+// eps (|mean| / spread)^2, so the caller takes the moments about a pivot near the clouds
+// (k_loop.hip corr_terms) and un-shifts the translation (pair_close_iteration).
 SE3ICP_HD M4 umeyama_from_moments(const double* s, double n) {
     if (!(n > 0)) return M4::eye();
     const double inv = 1.0 / n;
@@ -296,7 +299,8 @@ struct PairState {
 
 // Close the iteration just run (ISR.cpp:684-732) from the pair's 28 reduced values.
 // Sets S.done when the pair is finished, S.sw at the SE(3) -> R3 switch.
-SE3ICP_HD void pair_close_iteration(PairState& S, int est, const double* acc) {
+// piv: the pivot the pt2pt moments were taken about (PairDev::f32_center); none: the origin.
+SE3ICP_HD void pair_close_iteration(PairState& S, int est, const double* acc, const double* piv = nullptr) {
     // ISR.cpp:684-686 (mean of the kept distances; NaN when nothing is kept, as the reference)
     S.mse_prev = S.mse_cur;
     S.mse_cur = acc[27] / S.K;
@@ -304,7 +308,14 @@ SE3ICP_HD void pair_close_iteration(PairState& S, int est, const double* acc) {
     // ISR.cpp:689-703 estimator
     M4 Ti;
     if (S.K <= 0) Ti = M4::eye();
-    else if (est == EST_PT2PT) Ti = umeyama_from_moments(acc, acc[15]);
+    else if (est == EST_PT2PT) {
+        Ti = umeyama_from_moments(acc, acc[15]);
+        // the step about the pivot c is x -> R (x - c) + t + c: t <- t + c - R c.  Skipped,
+        // not computed, for a zero pivot (the normalized methods stay bitwise what they were)
+        if (piv && (piv[0] != 0.0 || piv[1] != 0.0 || piv[2] != 0.0))
+            for (int i = 0; i < 3; ++i)
+                Ti.m[i][3] += piv[i] - (Ti.m[i][0] * piv[0] + Ti.m[i][1] * piv[1] + Ti.m[i][2] * piv[2]);
+    }
     else Ti = solve_normal_equations(acc);
     // ISR.cpp:706-716: the source cloud and its SE(3) elements follow T on the fly
     const M4 Tprev = S.T;

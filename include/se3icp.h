@@ -98,7 +98,10 @@ typedef struct se3icp_result {
                                          registers its pairs in lockstep, and every pair gets
                                          the batch's setup / loop / NN / total time, not a
                                          per-pair share (the reference times one registration;
-                                         a batched caller divides by the batch size for a mean). */
+                                         a batched caller divides by the batch size for a mean).
+                                         After a sweep they are GROUP-WIDE: the shared setup plus
+                                         the group's own expansion and 12-D trees, and the group's
+                                         loop / NN times (parameter sweeps, below). */
 } se3icp_result;
 
 /* ------------------------------------------------------------- misc */
@@ -154,6 +157,42 @@ int se3icp_register_batch(int device, int32_t n_pairs, const double* const* src_
 int se3icp_register_batch_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
                                  const double* d_tgt_xyz, const int64_t* tgt_off, int method,
                                  const se3icp_params* params, se3icp_result* results, void* hip_stream);
+
+/* ------------------------------------------------------------- parameter sweeps
+ * The outer loop of the reference's benchmark drivers: the whole dataset registered once
+ * per value of a parameter grid (makeHybridLGrid(), examples/benchmark_kitti.cpp:354-393).
+ *
+ * Register every pair under every parameter set of `variants` with ONE setup.
+ * results[v * n_pairs + p]: pair p under variants[v], bitwise what
+ * se3icp_register_batch(..., &variants[v], ...) returns for pair p
+ * (T, num_iterations, num_pure_se3_iterations, status, scaling_factor;
+ * not the times, not num_rechecked).
+ * All variants share `method`, number_of_nn_for_LRF and scale_preprocessing
+ * (else SE3ICP_ERR_INVALID_ARG): those shape the shared setup.  Every other
+ * field may differ per variant.  The vanilla methods (pt2pt, pt2pl, gicp) have no frames:
+ * their sweep shares ingest, 3-D trees and normals and varies the loop parameters only.
+ * max_group: variants registered in lockstep at once (0 = engine's choice: up to 8, while
+ * a group stays within 2^26 points, device memory and the 2^30 points of a batch).
+ * Arguments are checked before the device is looked up (SE3ICP_ERR_INVALID_ARG for
+ * n_variants <= 0, variants == NULL, max_group < 0; SE3ICP_ERR_INVALID_METHOD;
+ * SE3ICP_ERR_EMPTY_CLOUD); without a device SE3ICP_ERR_NO_DEVICE, never a CPU fallback.
+ * Returns as se3icp_register_batch: OK, or SE3ICP_ERR_NONFINITE when some result is
+ * non-finite, each result's `status` set.
+ * Times of a result: time_setup_ms is the shared setup plus its group's expansion and 12-D
+ * trees; time_loop_ms and time_se3_correspondence_search_ms are its group's (GROUP-WIDE,
+ * as a batch's are batch-wide); time_before_pure_icp_ms as for a batch, from those two.
+ * se3icp_last_kernel_times(_n) after a sweep: the setup entries (lrf_*, setup_ms) are the one
+ * shared setup's, the loop entries are summed over the groups.
+ * se3icp_set_trace before a sweep: trace.pair indexes the result array, v * n_pairs + p; the
+ * group that holds it runs without look-ahead; the trace disarms after the call. */
+int se3icp_register_sweep(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                          const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
+                          const se3icp_params* variants, int32_t max_group, se3icp_result* results);
+/* Same, with the clouds resident in HBM (see se3icp_register_batch_device). */
+int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method, int32_t n_variants,
+                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
+                                 void* hip_stream);
 
 /* Single pair convenience (host buffers). */
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,

@@ -138,6 +138,62 @@ int se3icp_register_batch_device(int device, int32_t n_pairs, const double* d_sr
                              (hipStream_t)hip_stream);
 }
 
+// ------------------------------------------------------------------ parameter sweeps
+// The arguments of a sweep are checked before the device is looked up: a bad call is
+// reported as such on a host without a GPU too.
+static int sweep_check(int32_t n_pairs, const int64_t* n_src, const int64_t* n_tgt, int method, int32_t n_variants,
+                       const se3icp_params* variants, int32_t max_group, const se3icp_result* results) {
+    if (n_pairs <= 0 || !n_src || !n_tgt || !results) return SE3ICP_ERR_INVALID_ARG;
+    if (n_variants <= 0 || !variants || max_group < 0) return SE3ICP_ERR_INVALID_ARG;
+    if (method < 0 || method >= SE3ICP_NUM_METHODS) return SE3ICP_ERR_INVALID_METHOD;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (n_src[p] <= 0 || n_tgt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+    // what shapes the shared setup is common to all variants
+    for (int32_t v = 1; v < n_variants; ++v)
+        if (variants[v].number_of_nn_for_LRF != variants[0].number_of_nn_for_LRF ||
+            variants[v].scale_preprocessing != variants[0].scale_preprocessing)
+            return SE3ICP_ERR_INVALID_ARG;
+    if (method >= SE3ICP_SE3_PT2PT && variants[0].number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
+    return SE3ICP_OK;
+}
+
+int se3icp_register_sweep(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                          const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
+                          const se3icp_params* variants, int32_t max_group, se3icp_result* results) {
+    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
+    const int rc = sweep_check(n_pairs, n_src, n_tgt, method, n_variants, variants, max_group, results);
+    if (rc) return rc;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_sweep(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants, max_group,
+                             results, nullptr);
+}
+
+int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method, int32_t n_variants,
+                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
+                                 void* hip_stream) {
+    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
+    std::vector<const double*> s(n_pairs), t(n_pairs);
+    std::vector<int64_t> ns(n_pairs), nt(n_pairs);
+    for (int i = 0; i < n_pairs; ++i) {
+        s[i] = d_src_xyz + 3 * src_off[i];
+        t[i] = d_tgt_xyz + 3 * tgt_off[i];
+        ns[i] = src_off[i + 1] - src_off[i];
+        nt[i] = tgt_off[i + 1] - tgt_off[i];
+    }
+    const int rc = sweep_check(n_pairs, ns.data(), nt.data(), method, n_variants, variants, max_group, results);
+    if (rc) return rc;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_sweep(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, n_variants, variants,
+                             max_group, results, (hipStream_t)hip_stream);
+}
+
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,
                     int method, const se3icp_params* params, se3icp_result* result) {
     return se3icp_register_batch(device, 1, &src_xyz, &n_src, &tgt_xyz, &n_tgt, method, params, result);

@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 
+#include "sweep.hpp"
 #include "tree.hpp"
 
 namespace se3icp {
@@ -124,20 +125,23 @@ int Engine::init() {
     return 0;
 }
 
-Engine::~Engine() {
-    if (!ok_) return;
-    (void)hipSetDevice(dev_);
-    DevBuf* all[] = {&d_clouds_, &d_setup_, &d_pairs_, &d_cloud_of_, &d_inptr_, &d_in_, &d_xyz64_, &d_xyz32_,
+std::vector<DevBuf*> Engine::all_bufs() {
+    return {&d_clouds_, &d_setup_, &d_pairs_, &d_cloud_of_, &d_inptr_, &d_in_, &d_xyz64_, &d_xyz32_,
                      &d_fr64_, &d_fr32_, &d_nrm64_, &d_tgeo_, &d_conf64_, &d_knn_,
                      &d_corr_idx_, &d_corr_dist_, &d_flag_count_, &d_gcost_, &d_cls_, &d_trim_key_, &d_red_partial_,
                      &d_red_out_, &d_work_, &d_wb_, &d_wn_, &d_chunks_, &d_partial_, &d_centers_,
                      &d_rechecked_, &d_keys0_, &d_vals1_, &d_sort_tmp_, &d_stats_,
                      &d_qlist_, &d_qcount_, &d_hist_, &d_cert_, &d_sqlist_, &d_state_, &d_trim_cand_, &d_trim_ctr_, &d_scales_, &d_trim_hist_,
-                     &d_lrf_fb_, &d_lrf_fbn_, &d_big_d_, &d_big_i_,
+                     &d_lrf_fb_, &d_lrf_fbn_, &d_big_d_, &d_big_i_, &d_raw_, &d_sweep_w_,
                      &t3_.perm, &t3_.pos, &t3_.vec, &t3_.vec64, &t3_.vec64a, &t3_.blo, &t3_.bhi, &t3_.lo, &t3_.hi, &t3_.scr,
                      &t12_.perm, &t12_.pos, &t12_.vec, &t12_.vec64, &t12_.blo, &t12_.bhi, &t12_.lo, &t12_.hi, &t12_.scr,
                      &t12_.vecT};
-    for (DevBuf* b : all)
+}
+
+Engine::~Engine() {
+    if (!ok_) return;
+    (void)hipSetDevice(dev_);
+    for (DevBuf* b : all_bufs())
         if (b->p) (void)hipFree(b->p);
     if (h_pairs_) (void)hipHostFree(h_pairs_);
     if (h_red_) (void)hipHostFree(h_red_);
@@ -552,37 +556,10 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
     npairs_ = npairs;
     int64_t ntot = 0;
     for (int p = 0; p < npairs; ++p) ntot += ns[p] + nt[p];
-    // work table of k_reduce: one entry per kRedQ queries of every pair
-    int64_t soff = 0;
-    h_work_.clear();
-    h_wb_.assign(npairs, 0);
-    h_wn_.assign(npairs, 0);
-    for (int p = 0; p < npairs; ++p) {
-        h_wb_[p] = (int32_t)h_work_.size();
-        // (clouds are laid out src 0, tgt 0, src 1, ... as setup_clouds places them)
-        for (int64_t q0 = 0; q0 < ns[p]; q0 += kRedQ)
-            h_work_.push_back(BlockWork{p, (int32_t)q0, (int32_t)std::min<int64_t>(q0 + kRedQ, ns[p]), (int32_t)soff,
-                                        (int32_t)(soff + ns[p]), {0, 0, 0}});
-        soff += ns[p] + nt[p];
-        h_wn_[p] = (int32_t)h_work_.size() - h_wb_[p];
-    }
-    nwork_ = (int)h_work_.size();
     int rc = alloc_points(ntot, kmax);
     if (rc) return rc;
-    if (!ensure<PairDev>(d_pairs_, npairs) || !ensure<BlockWork>(d_work_, nwork_) || !ensure<int32_t>(d_wb_, npairs) ||
-        !ensure<int32_t>(d_wn_, npairs) || !ensure<uint64_t>(d_trim_key_, 2 * (size_t)npairs) ||
-        !ensure<unsigned long long>(d_trim_cand_, (size_t)npairs * kTrimList) || !ensure<unsigned>(d_trim_ctr_, 4 * (size_t)npairs) ||
-        !ensure<unsigned>(d_trim_hist_, 4096 * (size_t)npairs) ||
-        !ensure<double>(d_red_partial_, (size_t)nwork_ * kRedVals) || !ensure<double>(d_red_out_, (size_t)npairs * kRedVals) ||
-        !ensure<int32_t>(d_rechecked_, npairs))
-        return SE3ICP_ERR_OUT_OF_MEMORY;
-    if (pinned(h_pairs_, h_pairs_cap_, npairs) || pinned(h_red_, h_red_cap_, (size_t)npairs * kRedVals) ||
-        pinned(h_rechecked_, h_rechecked_cap_, npairs))
-        return SE3ICP_ERR_OUT_OF_MEMORY;
-    HIPCHK(hipMemcpyAsync(d_work_.p, h_work_.data(), sizeof(BlockWork) * nwork_, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_wb_.p, h_wb_.data(), sizeof(int32_t) * npairs, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_wn_.p, h_wn_.data(), sizeof(int32_t) * npairs, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_rechecked_.p, 0, sizeof(int32_t) * npairs, s));
+    rc = prepare_pairs(npairs, ns, nt, s);
+    if (rc) return rc;
 
     // ---- setup (ISR.cpp:568-648)
     std::vector<CloudReq> clouds(2 * npairs);
@@ -614,6 +591,49 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
     HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
     for (double& t : trace_prev_) t = 0;
     HIPCHK(hipEventRecord(ev_[13], s));
+    return run_loop(npairs, ns, mi.kind, mi.est, &prm, npairs, false, tr, out, s);
+}
+
+// Work table of k_reduce and the per-pair buffers of a batch (see engine.hpp).
+int Engine::prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipStream_t s) {
+    // work table of k_reduce: one entry per kRedQ queries of every pair
+    int64_t soff = 0;
+    h_work_.clear();
+    h_wb_.assign(npairs, 0);
+    h_wn_.assign(npairs, 0);
+    for (int p = 0; p < npairs; ++p) {
+        h_wb_[p] = (int32_t)h_work_.size();
+        // (clouds are laid out src 0, tgt 0, src 1, ... as setup_clouds places them)
+        for (int64_t q0 = 0; q0 < ns[p]; q0 += kRedQ)
+            h_work_.push_back(BlockWork{p, (int32_t)q0, (int32_t)std::min<int64_t>(q0 + kRedQ, ns[p]), (int32_t)soff,
+                                        (int32_t)(soff + ns[p]), {0, 0, 0}});
+        soff += ns[p] + nt[p];
+        h_wn_[p] = (int32_t)h_work_.size() - h_wb_[p];
+    }
+    nwork_ = (int)h_work_.size();
+    if (!ensure<PairDev>(d_pairs_, npairs) || !ensure<BlockWork>(d_work_, nwork_) || !ensure<int32_t>(d_wb_, npairs) ||
+        !ensure<int32_t>(d_wn_, npairs) || !ensure<uint64_t>(d_trim_key_, 2 * (size_t)npairs) ||
+        !ensure<unsigned long long>(d_trim_cand_, (size_t)npairs * kTrimList) || !ensure<unsigned>(d_trim_ctr_, 4 * (size_t)npairs) ||
+        !ensure<unsigned>(d_trim_hist_, 4096 * (size_t)npairs) ||
+        !ensure<double>(d_red_partial_, (size_t)nwork_ * kRedVals) || !ensure<double>(d_red_out_, (size_t)npairs * kRedVals) ||
+        !ensure<int32_t>(d_rechecked_, npairs))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    if (pinned(h_pairs_, h_pairs_cap_, npairs) || pinned(h_red_, h_red_cap_, (size_t)npairs * kRedVals) ||
+        pinned(h_rechecked_, h_rechecked_cap_, npairs))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    HIPCHK(hipMemcpyAsync(d_work_.p, h_work_.data(), sizeof(BlockWork) * nwork_, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_wb_.p, h_wb_.data(), sizeof(int32_t) * npairs, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_wn_.p, h_wn_.data(), sizeof(int32_t) * npairs, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_rechecked_.p, 0, sizeof(int32_t) * npairs, s));
+    return 0;
+}
+
+// Loop state, loop and results of the pairs of the batch that was set up (see engine.hpp).
+int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3icp_params* vprm,
+                     int pairs_per_variant, bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s) {
+    const MethodInfo mi{(Kind)kind, est};
+    const bool se3 = mi.kind != KIND_ICP;
+    int rc = 0;
 
     // ---- per-pair loop state (ISR.cpp:629-651); iteration 1 is opened here, every later
     // one by k_reduce_final on the device (pairmath.hpp), so the host only queues work
@@ -630,10 +650,20 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
             return SE3ICP_ERR_OUT_OF_MEMORY;
         h_phase_cap_ = want;
     }
-    const float ratio = std::min(1.0f, std::max(0.0f, (float)prm.estimated_overlap));  // PCL setOverlapRatio(float)
+    // what the host's queueing decisions read of the parameters, over all variants: SE(3)
+    // grids are queued up to the largest max_num_se3_iterations (without bound if any variant
+    // has none, "< 1"); they only decide which grids are queued, a pair's own limits are in
+    // its PairState
+    int se3_limit = 0;
+    for (int k = 0; k * pairs_per_variant < npairs; ++k) {
+        const int m = vprm[k].max_num_se3_iterations;
+        se3_limit = (m < 1 || se3_limit < 0) ? -1 : std::max(se3_limit, m);
+    }
     int n_se3 = 0, n_r3 = 0;
     bool any_trim = false;
     for (int p = 0; p < npairs; ++p) {
+        const se3icp_params& prm = vprm[p / pairs_per_variant];
+        const float ratio = std::min(1.0f, std::max(0.0f, (float)prm.estimated_overlap));  // PCL setOverlapRatio(float)
         PairState& S = h_state_[p];
         std::memset(&S, 0, sizeof(S));
         S.T = M4::eye();
@@ -696,7 +726,7 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
         for (int p = 0; p < npairs; ++p) h_phase_[(size_t)(it % kLoopRing) * npairs + p] = -1;
         // SE(3) phase: iterations 1..max_num_se3_iterations at most (ISR.cpp:718-723, 1118)
         const bool do_se3 =
-            n_se3 > 0 && (prm.max_num_se3_iterations < 1 || it <= prm.max_num_se3_iterations);
+            n_se3 > 0 && (se3_limit < 1 || it <= se3_limit);
         const bool do_r3 = n_r3 > 0 || (mi.kind != KIND_ICP && mi.kind != KIND_PURE && it >= 2);
         // HIP events around the NN grids always (bench.py's roofline); around every other
         // stage only when profiling (each marker costs the stream a few microseconds)
@@ -831,8 +861,10 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
     }
     HIPCHK(hipEventRecord(ev_[14], s));
     HIPCHK(hipMemcpyAsync(h_state_, d_state_.p, sizeof(PairState) * npairs, hipMemcpyDeviceToHost, s));
-    if (se3)  // the device's GetCenter results, for the de-normalization (h_partial_ holds >= 9 * nclouds)
-        HIPCHK(hipMemcpyAsync(h_partial_, d_centers_.p, sizeof(double) * 3 * nclouds_, hipMemcpyDeviceToHost, s));
+    // the device's GetCenter results, for the de-normalization (h_partial_ holds >= 9 * nclouds);
+    // replicas of a sweep group share their base clouds' centers
+    const int nbase = 2 * pairs_per_variant;
+    if (se3) HIPCHK(hipMemcpyAsync(h_partial_, d_centers_.p, sizeof(double) * 3 * nbase, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_rechecked_, d_rechecked_.p, sizeof(int32_t) * npairs, hipMemcpyDeviceToHost, s));
     {
         if (pinned(h_loop_stats_, h_loop_stats_cap_, (size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
@@ -843,16 +875,16 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
         double sum[kStatCols] = {};
         for (int i = 0; i < kStatSlots; ++i)
             for (int k = 0; k < kStatCols; ++k) sum[k] += (double)stats[kStatCols * i + k];
-        ktimes_.se3_dist_evals = sum[0];
-        ktimes_.se3_box_tests = sum[1];
-        ktimes_.r3_dist_evals = sum[2];
-        ktimes_.r3_box_tests = sum[3];
-        ktimes_.se3_queries = sum[4];
-        ktimes_.se3_searched = sum[5];
-        ktimes_.r3_queries = sum[6];
-        ktimes_.r3_searched = sum[7];
-        ktimes_.se3_useful_evals = sum[kStatUseSe3];
-        ktimes_.r3_useful_evals = sum[kStatUseR3];
+        ktimes_.se3_dist_evals += sum[0];
+        ktimes_.se3_box_tests += sum[1];
+        ktimes_.r3_dist_evals += sum[2];
+        ktimes_.r3_box_tests += sum[3];
+        ktimes_.se3_queries += sum[4];
+        ktimes_.se3_searched += sum[5];
+        ktimes_.r3_queries += sum[6];
+        ktimes_.r3_searched += sum[7];
+        ktimes_.se3_useful_evals += sum[kStatUseSe3];
+        ktimes_.r3_useful_evals += sum[kStatUseR3];
 #ifdef SE3ICP_PROF
         {
             const double nw = std::max(1.0, std::floor(sum[11] / 17592186044416.0));
@@ -870,17 +902,26 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
 #endif
     }
     float setup_ms = 0, loop_ms = 0;
-    HIPCHK(hipEventElapsedTime(&setup_ms, ev_[12], ev_[13]));
+    if (sweep) {
+        float shared_ms = 0, group_ms = 0;
+        HIPCHK(hipEventElapsedTime(&shared_ms, ev_[12], ev_[8]));
+        HIPCHK(hipEventElapsedTime(&group_ms, ev_[9], ev_[13]));
+        setup_ms = shared_ms + group_ms;
+        ktimes_.setup_ms = shared_ms;
+    } else {
+        HIPCHK(hipEventElapsedTime(&setup_ms, ev_[12], ev_[13]));
+        ktimes_.setup_ms = setup_ms;
+    }
     HIPCHK(hipEventElapsedTime(&loop_ms, ev_[13], ev_[14]));
-    ktimes_.setup_ms = setup_ms;
 
     int worst = 0;
     for (int p = 0; p < npairs; ++p) {
         const PairState& S = h_state_[p];
         M4 T = S.T;
         if (se3) {  // ISR.cpp:735-738 de-normalization
-            const double* cs = &h_partial_[3 * (2 * p)];
-            const double* ct = &h_partial_[3 * (2 * p + 1)];
+            const int bp = p % pairs_per_variant;
+            const double* cs = &h_partial_[3 * (2 * bp)];
+            const double* ct = &h_partial_[3 * (2 * bp + 1)];
             for (int r = 0; r < 3; ++r) {
                 const double Rc = T.m[r][0] * cs[0] + T.m[r][1] * cs[1] + T.m[r][2] * cs[2];
                 T.m[r][3] = (1.0 / S.sf) * T.m[r][3] - Rc + ct[r];
@@ -905,6 +946,187 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
         R.time_before_pure_icp_ms = mi.kind == KIND_CF ? (double)setup_ms + (double)loop_ms : 0.0;
         if (R.status != SE3ICP_OK) worst = R.status;
     }
+    return worst;
+}
+
+// ----------------------------------------------------------------------------- parameter sweep
+// One shared setup over the base clouds with alpha = beta = 1 (the stored rows are the raw
+// frame and the raw normalized point: 1.0 * x is exact), then the variants in groups: each
+// group is a batch of g * P virtual pairs -- the base slots are its first variant, replicas
+// 1 .. g-1 follow at point offset v * N -- expanded and weighted by k_sweep_expand, given
+// its 12-D trees and run through the loop.  A pair registers bitwise the same in any batch,
+// so every result equals that of register_batch with its variant.
+int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, const double* const* tgt,
+                           const int64_t* nt, bool on_device, int method, int nvariants,
+                           const se3icp_params* variants, int max_group, se3icp_result* out, hipStream_t user_stream) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    se3icp_trace* tr = trace_;  // one-shot: the record covers this sweep only
+    trace_ = nullptr;
+    if (P <= 0 || !src || !tgt || !ns || !nt || !out || nvariants <= 0 || !variants || max_group < 0)
+        return SE3ICP_ERR_INVALID_ARG;
+    if (tr && (tr->pair < 0 || (int64_t)tr->pair >= (int64_t)nvariants * P || tr->max_iters < 0))
+        return SE3ICP_ERR_INVALID_ARG;
+    if (tr) tr->iters_recorded = 0;
+    MethodInfo mi;
+    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
+    for (int p = 0; p < P; ++p) {
+        if (ns[p] <= 0 || nt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+        if (!src[p] || !tgt[p]) return SE3ICP_ERR_INVALID_ARG;
+    }
+    const se3icp_params& prm0 = variants[0];
+    for (int k = 1; k < nvariants; ++k)
+        if (variants[k].number_of_nn_for_LRF != prm0.number_of_nn_for_LRF ||
+            variants[k].scale_preprocessing != prm0.scale_preprocessing)
+            return SE3ICP_ERR_INVALID_ARG;
+    const bool se3 = mi.kind != KIND_ICP;
+    const int k_lrf = se3 ? prm0.number_of_nn_for_LRF : 0;
+    if (se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
+    int k_nrm_s = 0, k_nrm_t = 0;
+    if (mi.est == EST_PT2PL) k_nrm_t = 30;
+    if (mi.est == EST_GICP) { k_nrm_s = 20; k_nrm_t = 20; }
+    const int kmax = std::max({k_lrf, k_nrm_s, k_nrm_t, 1});
+    HIPCHK(hipSetDevice(dev_));
+    hipStream_t s = user_stream ? user_stream : stream_;
+    ktimes_ = KernelTimes{};
+    HIPCHK(hipEventRecord(ev_[12], s));
+
+    int64_t N = 0;
+    int max_n = 1;
+    for (int p = 0; p < P; ++p) {
+        N += ns[p] + nt[p];
+        max_n = (int)std::max<int64_t>(max_n, std::max(ns[p], nt[p]));
+    }
+    const int nbase = 2 * P;
+    // group size: what the caller allows, the point limit of a batch and the memory hold
+    // (free memory plus the buffers this engine would reuse)
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    int64_t held = 0;
+    for (DevBuf* b : all_bufs()) held += (int64_t)b->bytes;
+    const int G = sweep_group_size(nvariants, max_group, N, nbase, kSweepBytesPerPoint, kSweepBytesPerCloud,
+                                   (int64_t)free_b + held);
+    const int ngroups = sweep_num_groups(nvariants, G);
+
+    // buffers of the largest group, before the shared setup fills them (ensure() does not
+    // keep a buffer's contents when it grows)
+    int rc = alloc_points((int64_t)G * N, kmax);
+    if (rc) return rc;
+    const int nnodes3 = 2 << tree_depth_for(max_n);
+    const size_t nbox = (size_t)G * nbase * nnodes3 * 3;
+    if (!ensure<CloudDev>(d_clouds_, (size_t)G * nbase) || !ensure<CloudSetup>(d_setup_, (size_t)G * nbase) ||
+        !ensure<float>(t3_.lo, nbox) || !ensure<float>(t3_.hi, nbox) || !ensure<double>(d_scales_, (size_t)G * P) ||
+        !ensure<SweepWeight>(d_sweep_w_, G) || (se3 && !ensure<double>(d_raw_, 12 * (size_t)N)))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+
+    // ---- shared setup (ISR.cpp:568-648) of the base clouds
+    npairs_ = P;
+    ntot_ = N;  // (ld_ stays the group's: the SoA columns keep one stride through the sweep)
+    std::vector<CloudReq> clouds(nbase);
+    for (int p = 0; p < P; ++p) {
+        for (int side = 0; side < 2; ++side) {
+            CloudReq& r = clouds[2 * p + side];
+            r.in = side == 0 ? src[p] : tgt[p];
+            r.n = side == 0 ? ns[p] : nt[p];
+            CloudSetup& st = r.st;
+            st = CloudSetup{};
+            st.k_lrf = k_lrf;
+            st.k_nrm = side == 0 ? k_nrm_s : k_nrm_t;
+            st.k_knn = std::max(st.k_lrf, st.k_nrm);
+            st.want_cov = mi.est == EST_GICP;
+            st.want_conf = mi.kind == KIND_CF;
+            st.is_target = side == 1;
+            st.cf_target = 0;  // (the rows are weighted, and a cf target's f32 rows formed, per variant)
+            st.alpha = 1.0;
+            st.beta = 1.0;
+            st.norm_scale = 1.0;
+        }
+    }
+    rc = setup_clouds(clouds, on_device, se3, prm0.scale_preprocessing, false, nullptr, nullptr, s);
+    if (rc) return rc;
+    if (se3)
+        HIPCHK(hipMemcpyAsync(d_raw_.p, d_fr64_.p, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipEventRecord(ev_[8], s));
+    const std::vector<CloudDev> base_clouds = h_clouds_;
+    const std::vector<CloudSetup> base_setup = h_setup_;
+
+    std::vector<int64_t> vns((size_t)G * P), vnt((size_t)G * P);
+    for (int q = 0; q < G * P; ++q) {
+        vns[q] = ns[q % P];
+        vnt[q] = nt[q % P];
+    }
+    std::vector<std::vector<SweepWeight>> weights(ngroups);  // (alive until the copies have run)
+    int worst = 0;
+    for (int gi = 0; gi < ngroups; ++gi) {
+        int v0 = 0, g = 0;
+        sweep_group(nvariants, G, gi, &v0, &g);
+        HIPCHK(hipEventRecord(ev_[9], s));
+        // ---- the group's batch: g * P virtual pairs over g * 2P virtual clouds
+        nclouds_ = g * nbase;
+        npairs_ = g * P;
+        ntot_ = (int64_t)g * N;
+        h_clouds_.resize(nclouds_);
+        h_setup_.resize(nclouds_);
+        std::vector<SweepWeight>& w = weights[gi];
+        w.resize(g);
+        for (int k = 0; k < g; ++k) {
+            w[k] = SweepWeight{variants[v0 + k].alpha_rot, variants[v0 + k].beta_transl};
+            for (int c = 0; c < nbase; ++c) {
+                h_clouds_[k * nbase + c] = CloudDev{(int32_t)(base_clouds[c].off + (int64_t)k * N), base_clouds[c].n};
+                CloudSetup st = base_setup[c];
+                st.alpha = w[k].alpha;
+                st.beta = w[k].beta;
+                st.cf_target = (mi.kind == KIND_CF && st.is_target) ? 1 : 0;
+                h_setup_[k * nbase + c] = st;  // (host mirror; the device's is written by k_sweep_expand)
+            }
+        }
+        HIPCHK(hipMemcpyAsync(d_sweep_w_.p, w.data(), sizeof(SweepWeight) * g, hipMemcpyHostToDevice, s));
+        SweepArgs a{};
+        a.g = g;
+        a.n = (int32_t)N;
+        a.nclouds = nbase;
+        a.nnodes3 = nnodes3;
+        a.frames = se3 ? 1 : 0;
+        a.cf = mi.kind == KIND_CF ? 1 : 0;
+        a.raw = (const double*)d_raw_.p;
+        a.w = (const SweepWeight*)d_sweep_w_.p;
+        a.scales = se3 ? (double*)d_scales_.p : nullptr;
+        a.tpt64 = (double4*)t3_.vec64a.p;
+        a.perm3 = (int32_t*)t3_.perm.p;
+        a.pos3 = (int32_t*)t3_.pos.p;
+        a.tvec3 = (float*)t3_.vec.p;
+        a.tvec64_3 = (double*)t3_.vec64.p;
+        a.lo3 = (float*)t3_.lo.p;
+        a.hi3 = (float*)t3_.hi.p;
+        launch_sweep_expand(view(), a, s);
+        HIPCHK(hipGetLastError());
+        have12_ = se3;
+        if (se3) {
+            rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
+            if (rc) return rc;
+        }
+        rc = prepare_pairs(g * P, vns.data(), vnt.data(), s);
+        if (rc) return rc;
+        rc = setup_chunks(g * P, s);
+        if (rc) return rc;
+        HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * ld_, s));  // no previous match yet
+        HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
+        for (double& t : trace_prev_) t = 0;
+        HIPCHK(hipEventRecord(ev_[13], s));
+        // the armed trace, if its pair is in this group (result index v * P + p)
+        se3icp_trace gtr{};
+        se3icp_trace* use = nullptr;
+        if (tr && tr->pair >= v0 * P && tr->pair < (v0 + g) * P) {
+            gtr = *tr;
+            gtr.pair = tr->pair - v0 * P;
+            use = &gtr;
+        }
+        rc = run_loop(g * P, vns.data(), mi.kind, mi.est, variants + v0, P, true, use, out + (size_t)v0 * P, s);
+        if (use) tr->iters_recorded = gtr.iters_recorded;
+        if (rc && rc != SE3ICP_ERR_NONFINITE) return rc;
+        if (rc) worst = rc;
+    }
+    // (ktimes_: the setup entries are the shared setup's, read at the first group's
+    // synchronisation; the loop entries were summed over the groups)
     return worst;
 }
 

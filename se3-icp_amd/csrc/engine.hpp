@@ -59,6 +59,11 @@ class Engine {
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
                        const int64_t* nt, bool on_device, int method, const se3icp_params& prm,
                        se3icp_result* out, hipStream_t user_stream);
+    // Every pair under every parameter set of `variants`, results[v * npairs + p], with one
+    // shared setup (sweep.hpp); the caller has validated the arguments (capi.cpp).
+    int register_sweep(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
+                       const int64_t* nt, bool on_device, int method, int nvariants, const se3icp_params* variants,
+                       int max_group, se3icp_result* out, hipStream_t user_stream);
 
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
@@ -89,6 +94,17 @@ class Engine {
     int setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool normalize_pairs, double scale_pre,
                      bool build12, std::vector<double>* centers, std::vector<double>* scales, hipStream_t s);
     int setup_chunks(int npairs, hipStream_t s);
+    // the two halves of a registration around setup_clouds.  prepare_pairs: the work table
+    // of k_reduce and the per-pair buffers of a batch of npairs pairs laid out src 0, tgt 0,
+    // src 1, ...; run_loop: loop state, the loop and the results of those pairs.  Pair q
+    // takes its parameters from vprm[q / pairs_per_variant] (a plain batch: one variant of
+    // npairs pairs; a sweep group: the group's variants, pair q a replica of base pair
+    // q % pairs_per_variant).  sweep: the setup time is the shared setup's (events 12 -> 8)
+    // plus the group's (9 -> 13) instead of 12 -> 13.
+    int prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipStream_t s);
+    int run_loop(int npairs, const int64_t* ns, int kind, int est, const se3icp_params* vprm, int pairs_per_variant,
+                 bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s);
+    std::vector<DevBuf*> all_bufs();
     int read_lrf_stats();
     int sync_stream(hipStream_t s);
     View view() const;
@@ -131,7 +147,8 @@ class Engine {
         d_rechecked_, d_keys0_, d_vals1_, d_sort_tmp_, d_stats_, d_qlist_, d_qcount_, d_hist_, d_cert_,
         d_sqlist_, d_state_, d_trim_cand_, d_trim_ctr_, d_scales_, d_trim_hist_,
         d_lrf_fb_, d_lrf_fbn_,  // k_lrf8 -> exact k_lrf hand-over list and its count
-        d_big_d_, d_big_i_;     // k_knn_big candidate buffers (neighbourhoods over kSmallK)
+        d_big_d_, d_big_i_,     // k_knn_big candidate buffers (neighbourhoods over kSmallK)
+        d_raw_, d_sweep_w_;     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
     TreeBufs t3_, t12_;
     // pinned host mirrors
     PairDev* h_pairs_ = nullptr;
@@ -152,7 +169,7 @@ class Engine {
     size_t h_loop_stats_cap_ = 0;
     bool lrf_stats_pending_ = false;
     // 6/7: k_lrf time; 12/13/14: batch begin / setup done / loop done (GPU-timeline phase
-    // times); 15: sync_stream; the rest unused
+    // times); 8/9: a sweep's shared setup done / group begin; 15: sync_stream; the rest unused
     hipEvent_t ev_[16];
     // loop iterations in flight: kernel-time events and launched NN phases per ring slot
     static constexpr int kLoopRing = 4, kLoopEv = 7;

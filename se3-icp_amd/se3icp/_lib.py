@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_params_of", "se3icp_run_icp", "se3icp_run_se3_icp", "se3icp_run_se3_icp_with_cf", "se3icp_run_se3_pure",
     "se3icp_get_result",
     "se3icp_register_batch", "se3icp_register_batch_device", "se3icp_register",
+    "se3icp_register_sweep", "se3icp_register_sweep_device",
     "se3icp_toldi_frames", "se3icp_knn_self", "se3icp_estimate_normals", "se3icp_nn",
     "se3icp_synthetic_pairs", "se3icp_synthetic_reference", "se3icp_synthetic_reference_device",
     "se3icp_random_downsample",
@@ -137,6 +138,12 @@ def load():
                                         C.POINTER(C.c_int64), C.c_int, C.POINTER(Params), C.POINTER(Result)]
     L.se3icp_register_batch_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), vp,
                                                C.POINTER(C.c_int64), C.c_int, C.POINTER(Params), C.POINTER(Result), vp]
+    L.se3icp_register_sweep.argtypes = [C.c_int, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.POINTER(dp),
+                                        C.POINTER(C.c_int64), C.c_int, C.c_int32, C.POINTER(Params), C.c_int32,
+                                        C.POINTER(Result)]
+    L.se3icp_register_sweep_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), vp,
+                                               C.POINTER(C.c_int64), C.c_int, C.c_int32, C.POINTER(Params), C.c_int32,
+                                               C.POINTER(Result), vp]
     L.se3icp_register.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(Params),
                                   C.POINTER(Result)]
     L.se3icp_toldi_frames.argtypes = [C.c_int, dp, C.c_int64, C.c_int, dp]

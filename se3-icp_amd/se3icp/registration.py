@@ -378,6 +378,121 @@ def register_batch_traced(pairs, method: str, params: _lib.Params | None = None,
     return res, {k: v[:n] for k, v in tr.items()}
 
 
+# ---- parameter sweeps (the outer loop of the reference's benchmark drivers)
+def alpha_grid() -> list[float]:
+    """The 47 values of alpha_rot the reference's drivers sweep: makeHybridLGrid()
+    (examples/benchmark_kitti.cpp:354-384, the same in the lounge, synthetic and pure-SE(3)
+    drivers), with its double arithmetic: 0, i * 0.01 (i = 1..10), i * 0.1 (i = 2..10),
+    1.0 + i * 0.5 (i = 0..8), the literal tail, sorted, duplicates removed."""
+    g = [0.0]
+    g += [i * 0.01 for i in range(1, 11)]
+    g += [i * 0.1 for i in range(2, 11)]
+    g += [1.0 + i * 0.5 for i in range(0, 9)]
+    g += [5.0, 7.0, 10.0, 15.0, 25.0, 50.0, 60.0, 70.0, 80.0, 90.0, 100.0, 200.0, 300.0, 400.0, 500.0, 600.0, 700.0,
+          800.0, 900.0, 1000.0]
+    return sorted(set(g))
+
+
+def _copy_params(p: _lib.Params) -> _lib.Params:
+    q = _lib.Params()
+    C.memmove(C.byref(q), C.byref(p), C.sizeof(_lib.Params))
+    return q
+
+
+def sweep_params(base: _lib.Params | None = None, **lists) -> list[_lib.Params]:
+    """The variants of a sweep: copies of ``base`` with the listed fields replaced, entry i
+    taking element i of every list (lists of one length), e.g.
+    ``sweep_params(kitti_params(), alpha_rot=alpha_grid())``."""
+    base = base or _lib.default_params()
+    lens = {len(v) for v in lists.values()}
+    if len(lens) != 1:
+        raise ValueError("sweep_params: give at least one list, all of one length")
+    fields = {f[0] for f in _lib.Params._fields_}
+    out = []
+    for i in range(lens.pop()):
+        q = _copy_params(base)
+        for k, vals in lists.items():
+            if k not in fields or k.startswith("_"):
+                raise ValueError(f"sweep_params: no parameter {k!r}")
+            setattr(q, k, vals[i])
+        out.append(q)
+    return out
+
+
+def _variant_array(variants):
+    nv = len(variants)
+    arr = (_lib.Params * nv)()
+    for i, p in enumerate(variants):
+        C.memmove(C.byref(arr, i * C.sizeof(_lib.Params)), C.byref(p), C.sizeof(_lib.Params))
+    return arr
+
+
+def _sweep_results(res, nv, n) -> list[list[PairResult]]:
+    flat = _results(res, nv * n)
+    return [flat[v * n:(v + 1) * n] for v in range(nv)]
+
+
+def register_sweep(pairs, method: str, variants, device: int = 0, max_group: int = 0) -> list[list[PairResult]]:
+    """Register every pair under every parameter set of ``variants`` (a list of Params that
+    share number_of_nn_for_LRF and scale_preprocessing) with one shared setup; result
+    ``[v][p]`` is bitwise what ``register_batch(pairs, method, variants[v])[p]`` returns.
+    max_group: variants registered in lockstep at once (0: the engine's choice)."""
+    L = _lib.load()
+    srcs = [_as_xyz(s) for s, _ in pairs]
+    tgts = [_as_xyz(t) for _, t in pairs]
+    n, nv = len(pairs), len(variants)
+    dp = C.POINTER(C.c_double)
+    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
+    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
+    ns = (C.c_int64 * n)(*[a.shape[0] for a in srcs])
+    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
+    res = (_lib.Result * max(1, nv * n))()
+    rc = L.se3icp_register_sweep(device, n, sp, ns, tp, nt, _lib.method_id(method), nv,
+                                 _variant_array(variants) if nv else None, max_group, res)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_sweep")
+    return _sweep_results(res, nv, n)
+
+
+def register_sweep_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str, variants, device: int = 0,
+                          stream: int = 0, max_group: int = 0) -> list[list[PairResult]]:
+    """register_sweep for clouds already in HBM (arguments as register_batch_device)."""
+    L = _lib.load()
+    n, nv = len(src_off) - 1, len(variants)
+    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
+    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
+    res = (_lib.Result * max(1, nv * n))()
+    rc = L.se3icp_register_sweep_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
+                                        _lib.method_id(method), nv, _variant_array(variants) if nv else None,
+                                        max_group, res, C.c_void_p(stream) if stream else None)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_sweep_device")
+    return _sweep_results(res, nv, n)
+
+
+def register_sweep_traced(pairs, method: str, variants, variant: int = 0, pair: int = 0, max_iters: int = 160,
+                          device: int = 0, max_group: int = 0):
+    """register_sweep with the per-iteration record of pair ``pair`` under variant ``variant``
+    (see register_batch_traced).  Returns (results, trace dict)."""
+    L = _lib.load()
+    ns = _as_xyz(pairs[pair][0]).shape[0]
+    tr = {"corr_idx": np.full((max_iters, ns), -1, np.int32), "corr_dist": np.zeros((max_iters, ns), np.float32),
+          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
+          "phase": np.zeros(max_iters, np.int32)}
+    t = _lib.Trace(variant * len(pairs) + pair, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
+                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
+                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(C.POINTER(C.c_double)),
+                   tr["mse"].ctypes.data_as(C.POINTER(C.c_double)), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)),
+                   0, 0)
+    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
+    try:
+        res = register_sweep(pairs, method, variants, device, max_group)
+    finally:
+        L.se3icp_set_trace(device, None)
+    n = int(t.iters_recorded)
+    return res, {k: v[:n] for k, v in tr.items()}
+
+
 # ---- stage entry points (one per reference function on the hot path)
 def toldi_frames(pts, k: int, device: int = 0) -> np.ndarray:
     """computeAllTOLDISE3FramesOMP (ISR.cpp:318-331): (N, 4, 4) frames."""

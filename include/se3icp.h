@@ -194,6 +194,75 @@ int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_sr
                                  const se3icp_params* variants, int32_t max_group, se3icp_result* results,
                                  void* hip_stream);
 
+/* ------------------------------------------------------------- registration reports
+ * What says whether a pose is any good, evaluated at the FINAL pose as Open3D's
+ * RegistrationResult and GetInformationMatrixFromPointClouds are.  For every source point i
+ * (all of them, no trimming) j(i) is the exact f64 nearest target point of T p_i (lowest
+ * index on exact ties) and d_i = |T p_i - x_j|, searched in the engine's frame and reported
+ * in the caller's units.  Point i is an inlier iff d_i <= max_correspondence_distance
+ * (compared squared, in f64, in the engine's frame); a distance <= 0 or +inf makes every
+ * point an inlier, NaN is SE3ICP_ERR_INVALID_ARG.
+ * The *_report entries return the same se3icp_result as their plain entries, bit for bit
+ * (T, both iteration counts, status, scaling_factor): the report runs after the loop and
+ * never writes the loop's state.  time_loop_ms does not include it. */
+typedef enum se3icp_stop_reason {
+    SE3ICP_STOP_CONVERGED = 0,           /* the method's MSE criterion held (also: a max_num_iterations the
+                                            SE(3) phase had already passed by) */
+    SE3ICP_STOP_MAX_ITERATIONS = 1,      /* num_iterations reached max_num_iterations */
+    SE3ICP_STOP_MAX_SE3_ITERATIONS = 2,  /* run_se3_pure: max_num_se3_iterations reached */
+    SE3ICP_STOP_RUNAWAY = 3              /* the engine's 100,000-iteration guard */
+} se3icp_stop_reason;
+
+typedef struct se3icp_report_options {
+    double max_correspondence_distance;  /* caller's units; <= 0 or +inf: every point is an inlier */
+    int32_t* corr_idx;                   /* optional [sum n_src]: j(i), pair p at the prefix sum of n_src */
+    double* corr_dist;                   /* optional [sum n_src]: d_i, same layout */
+    int32_t outputs_on_device;           /* the two buffers are device pointers */
+    int32_t _reserved;
+} se3icp_report_options;
+
+typedef struct se3icp_report {
+    double fitness;            /* n_inliers / n_src */
+    double inlier_rmse;        /* sqrt(sum d_i^2 / n_inliers) over the inliers; 0 without one */
+    double information[36];    /* row-major sum G^T G over the inliers, G = [-[x]x  I] of the target point x
+                                  (caller's coordinates; rotation first); zeros without an inlier */
+    double final_mse;          /* the loop's last MSE and its last change (normalized units, */
+    double final_mse_change;   /* see scaling_factor) */
+    int64_t n_inliers;
+    int32_t switched;          /* the run switched from SE(3) to R3 correspondences */
+    int32_t stop_reason;       /* se3icp_stop_reason; when a cap and the criterion hold in the same
+                                  iteration the cap is reported (the order of the reference's tests) */
+} se3icp_report;
+
+int se3icp_report_version(void);  /* 1 */
+
+/* se3icp_register_batch(_device) plus a report per pair.  opts and reports must not be NULL. */
+int se3icp_register_batch_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                                 const double* const* tgt_xyz, const int64_t* n_tgt, int method,
+                                 const se3icp_params* params, se3icp_result* results,
+                                 const se3icp_report_options* opts, se3icp_report* reports);
+int se3icp_register_batch_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                        const double* d_tgt_xyz, const int64_t* tgt_off, int method,
+                                        const se3icp_params* params, se3icp_result* results, void* hip_stream,
+                                        const se3icp_report_options* opts, se3icp_report* reports);
+/* se3icp_register_sweep(_device) plus reports[v * n_pairs + p].  The per-point buffers of
+ * opts must be NULL (SE3ICP_ERR_INVALID_ARG otherwise). */
+int se3icp_register_sweep_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                                 const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
+                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
+                                 const se3icp_report_options* opts, se3icp_report* reports);
+int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                        const double* d_tgt_xyz, const int64_t* tgt_off, int method,
+                                        int32_t n_variants, const se3icp_params* variants, int32_t max_group,
+                                        se3icp_result* results, void* hip_stream,
+                                        const se3icp_report_options* opts, se3icp_report* reports);
+/* Object surface: ask for a report before a run_*, read it after.  The per-point buffers of
+ * opts (host pointers, n_src entries) must stay valid until the run returns; opts == NULL
+ * withdraws the request.  se3icp_get_report: SE3ICP_ERR_INVALID_ARG when none was requested
+ * or no run has produced one. */
+int se3icp_request_report(se3icp_registration* r, const se3icp_report_options* opts);
+int se3icp_get_report(const se3icp_registration* r, se3icp_report* out);
+
 /* Single pair convenience (host buffers). */
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,
                     int method, const se3icp_params* params, se3icp_result* result);

@@ -51,6 +51,10 @@ struct se3icp_registration {
     std::vector<double> src, tgt;
     se3icp_params prm;
     se3icp_result res;
+    // se3icp_request_report: the options of the next run's report, and the last report
+    bool want_report = false, have_report = false;
+    se3icp_report_options ropts{};
+    se3icp_report rep{};
 };
 
 extern "C" {
@@ -194,6 +198,118 @@ int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_sr
                              max_group, results, (hipStream_t)hip_stream);
 }
 
+// ------------------------------------------------------------------ registration reports
+// Checked before the device is looked up, as the sweeps' arguments are.
+int se3icp_report_version(void) { return 1; }
+
+// the per-pair pointers and sizes of clouds concatenated in HBM (the *_device entries)
+static void pair_ranges(int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off, const double* d_tgt_xyz,
+                        const int64_t* tgt_off, std::vector<const double*>& s, std::vector<const double*>& t,
+                        std::vector<int64_t>& ns, std::vector<int64_t>& nt) {
+    s.resize(n_pairs); t.resize(n_pairs); ns.resize(n_pairs); nt.resize(n_pairs);
+    for (int i = 0; i < n_pairs; ++i) {
+        s[i] = d_src_xyz + 3 * src_off[i];
+        t[i] = d_tgt_xyz + 3 * tgt_off[i];
+        ns[i] = src_off[i + 1] - src_off[i];
+        nt[i] = tgt_off[i + 1] - tgt_off[i];
+    }
+}
+
+static int report_check(const se3icp_report_options* opts, const se3icp_report* reports, bool per_point_allowed) {
+    if (!opts || !reports) return SE3ICP_ERR_INVALID_ARG;
+    if (std::isnan(opts->max_correspondence_distance)) return SE3ICP_ERR_INVALID_ARG;
+    if (!per_point_allowed && (opts->corr_idx || opts->corr_dist)) return SE3ICP_ERR_INVALID_ARG;
+    return SE3ICP_OK;
+}
+
+static int batch_check(int32_t n_pairs, const int64_t* n_src, const int64_t* n_tgt, int method,
+                       const se3icp_params* params, const se3icp_result* results) {
+    if (n_pairs <= 0 || !n_src || !n_tgt || !results) return SE3ICP_ERR_INVALID_ARG;
+    if (method < 0 || method >= SE3ICP_NUM_METHODS) return SE3ICP_ERR_INVALID_METHOD;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (n_src[p] <= 0 || n_tgt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+    if (method >= SE3ICP_SE3_PT2PT && params && params->number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
+    return SE3ICP_OK;
+}
+
+int se3icp_register_batch_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                                 const double* const* tgt_xyz, const int64_t* n_tgt, int method,
+                                 const se3icp_params* params, se3icp_result* results,
+                                 const se3icp_report_options* opts, se3icp_report* reports) {
+    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
+    int rc = report_check(opts, reports, true);
+    if (rc) return rc;
+    rc = batch_check(n_pairs, n_src, n_tgt, method, params, results);
+    if (rc) return rc;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    se3icp_params p;
+    if (params) p = *params; else se3icp_default_params(&p);
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_batch(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, p, results, nullptr, opts, reports);
+}
+
+int se3icp_register_batch_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                        const double* d_tgt_xyz, const int64_t* tgt_off, int method,
+                                        const se3icp_params* params, se3icp_result* results, void* hip_stream,
+                                        const se3icp_report_options* opts, se3icp_report* reports) {
+    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
+    int rc = report_check(opts, reports, true);
+    if (rc) return rc;
+    std::vector<const double*> s, t;
+    std::vector<int64_t> ns, nt;
+    pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, s, t, ns, nt);
+    rc = batch_check(n_pairs, ns.data(), nt.data(), method, params, results);
+    if (rc) return rc;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    se3icp_params p;
+    if (params) p = *params; else se3icp_default_params(&p);
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_batch(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, p, results,
+                             (hipStream_t)hip_stream, opts, reports);
+}
+
+int se3icp_register_sweep_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                                 const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
+                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
+                                 const se3icp_report_options* opts, se3icp_report* reports) {
+    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
+    int rc = report_check(opts, reports, false);
+    if (rc) return rc;
+    rc = sweep_check(n_pairs, n_src, n_tgt, method, n_variants, variants, max_group, results);
+    if (rc) return rc;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_sweep(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants, max_group,
+                             results, nullptr, opts, reports);
+}
+
+int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                        const double* d_tgt_xyz, const int64_t* tgt_off, int method,
+                                        int32_t n_variants, const se3icp_params* variants, int32_t max_group,
+                                        se3icp_result* results, void* hip_stream,
+                                        const se3icp_report_options* opts, se3icp_report* reports) {
+    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
+    int rc = report_check(opts, reports, false);
+    if (rc) return rc;
+    std::vector<const double*> s, t;
+    std::vector<int64_t> ns, nt;
+    pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, s, t, ns, nt);
+    rc = sweep_check(n_pairs, ns.data(), nt.data(), method, n_variants, variants, max_group, results);
+    if (rc) return rc;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_sweep(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, n_variants, variants,
+                             max_group, results, (hipStream_t)hip_stream, opts, reports);
+}
+
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,
                     int method, const se3icp_params* params, se3icp_result* result) {
     return se3icp_register_batch(device, 1, &src_xyz, &n_src, &tgt_xyz, &n_tgt, method, params, result);
@@ -232,8 +348,15 @@ static int run_object(se3icp_registration* r, int method) {
     const double* s = r->src.data();
     const double* t = r->tgt.data();
     se3icp_result res;
-    int rc = se3icp_register_batch(current_device(), 1, &s, &ns, &t, &nt, method, &r->prm, &res);
-    if (rc == SE3ICP_OK || rc == SE3ICP_ERR_NONFINITE) r->res = res;
+    se3icp_report rep;
+    int rc = r->want_report ? se3icp_register_batch_report(current_device(), 1, &s, &ns, &t, &nt, method, &r->prm, &res,
+                                                           &r->ropts, &rep)
+                            : se3icp_register_batch(current_device(), 1, &s, &ns, &t, &nt, method, &r->prm, &res);
+    if (rc == SE3ICP_OK || rc == SE3ICP_ERR_NONFINITE) {
+        r->res = res;
+        r->have_report = r->want_report;
+        if (r->want_report) r->rep = rep;
+    }
     return rc;
 }
 
@@ -296,6 +419,24 @@ int se3icp_run_se3_pure(se3icp_registration* r, const char* variant) {
 int se3icp_get_result(const se3icp_registration* r, se3icp_result* out) {
     if (!r || !out) return SE3ICP_ERR_INVALID_ARG;
     *out = r->res;
+    return 0;
+}
+
+int se3icp_request_report(se3icp_registration* r, const se3icp_report_options* opts) {
+    if (!r) return SE3ICP_ERR_INVALID_ARG;
+    if (!opts) {
+        r->want_report = false;
+        return 0;
+    }
+    if (std::isnan(opts->max_correspondence_distance) || opts->outputs_on_device) return SE3ICP_ERR_INVALID_ARG;
+    r->ropts = *opts;
+    r->want_report = true;
+    return 0;
+}
+
+int se3icp_get_report(const se3icp_registration* r, se3icp_report* out) {
+    if (!r || !out || !r->have_report) return SE3ICP_ERR_INVALID_ARG;
+    *out = r->rep;
     return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 
+#include "report.hpp"
 #include "sweep.hpp"
 #include "tree.hpp"
 
@@ -133,6 +134,7 @@ std::vector<DevBuf*> Engine::all_bufs() {
                      &d_rechecked_, &d_keys0_, &d_vals1_, &d_sort_tmp_, &d_stats_,
                      &d_qlist_, &d_qcount_, &d_hist_, &d_cert_, &d_sqlist_, &d_state_, &d_trim_cand_, &d_trim_ctr_, &d_scales_, &d_trim_hist_,
                      &d_lrf_fb_, &d_lrf_fbn_, &d_big_d_, &d_big_i_, &d_raw_, &d_sweep_w_,
+                     &d_rep_partial_, &d_rep_out_, &d_rep_off_, &d_rep_idx_, &d_rep_dist_,
                      &t3_.perm, &t3_.pos, &t3_.vec, &t3_.vec64, &t3_.vec64a, &t3_.blo, &t3_.bhi, &t3_.lo, &t3_.hi, &t3_.scr,
                      &t12_.perm, &t12_.pos, &t12_.vec, &t12_.vec64, &t12_.blo, &t12_.bhi, &t12_.lo, &t12_.hi, &t12_.scr,
                      &t12_.vecT};
@@ -148,6 +150,7 @@ Engine::~Engine() {
     if (h_partial_) (void)hipHostFree(h_partial_);
     if (h_rechecked_) (void)hipHostFree(h_rechecked_);
     if (h_hist_) (void)hipHostFree(h_hist_);
+    if (h_rep_) (void)hipHostFree(h_rep_);
     if (h_lrf_stats_) (void)hipHostFree(h_lrf_stats_);
     if (h_loop_stats_) (void)hipHostFree(h_loop_stats_);
     for (auto& e : ev_)
@@ -526,7 +529,8 @@ int Engine::setup_chunks(int npairs, hipStream_t s) {
 // ----------------------------------------------------------------------------- batch registration
 int Engine::register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
                            const int64_t* nt, bool on_device, int method, const se3icp_params& prm,
-                           se3icp_result* out, hipStream_t user_stream) {
+                           se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
+                           se3icp_report* reports) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
     se3icp_trace* tr = trace_;  // one-shot: the record covers this batch only
     trace_ = nullptr;
@@ -591,7 +595,8 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
     HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
     for (double& t : trace_prev_) t = 0;
     HIPCHK(hipEventRecord(ev_[13], s));
-    return run_loop(npairs, ns, mi.kind, mi.est, &prm, npairs, false, tr, out, s);
+    const ReportReq rq{ropts, reports};
+    return run_loop(npairs, ns, mi.kind, mi.est, &prm, npairs, false, tr, out, s, (ropts && reports) ? &rq : nullptr);
 }
 
 // Work table of k_reduce and the per-pair buffers of a batch (see engine.hpp).
@@ -630,7 +635,8 @@ int Engine::prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipS
 
 // Loop state, loop and results of the pairs of the batch that was set up (see engine.hpp).
 int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3icp_params* vprm,
-                     int pairs_per_variant, bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s) {
+                     int pairs_per_variant, bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s,
+                     const ReportReq* rq) {
     const MethodInfo mi{(Kind)kind, est};
     const bool se3 = mi.kind != KIND_ICP;
     int rc = 0;
@@ -871,6 +877,12 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
         const unsigned long long* stats = h_loop_stats_;
         HIPCHK(hipMemcpyAsync(h_loop_stats_, d_stats_.p, sizeof(unsigned long long) * kStatCols * kStatSlots,
                               hipMemcpyDeviceToHost, s));
+        // the report stage, behind the loop's end event and every copy of the loop's results:
+        // what it adds to the counters and rewrites of PairDev is read by nobody
+        if (rq) {
+            rc = queue_report(npairs, ns, *rq, s);
+            if (rc) return rc;
+        }
         SYNC_STREAM(s);
         double sum[kStatCols] = {};
         for (int i = 0; i < kStatSlots; ++i)
@@ -918,8 +930,19 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
     for (int p = 0; p < npairs; ++p) {
         const PairState& S = h_state_[p];
         M4 T = S.T;
+        const int bp = p % pairs_per_variant;  // (a replica takes its base pair's centers)
+        if (rq) {
+            se3icp_report& Q = rq->out[p];
+            std::memset(&Q, 0, sizeof(Q));
+            const double origin[3] = {0.0, 0.0, 0.0};
+            report_expand(h_rep_ + (size_t)kRepVals * p, S.sf, h_pairs_[p].f32_center,
+                          se3 ? &h_partial_[3 * (2 * bp + 1)] : origin, ns[p], &Q);
+            Q.final_mse = S.mse_cur;
+            Q.final_mse_change = S.rel;
+            Q.switched = S.sw;
+            Q.stop_reason = report_stop_reason(S);
+        }
         if (se3) {  // ISR.cpp:735-738 de-normalization
-            const int bp = p % pairs_per_variant;
             const double* cs = &h_partial_[3 * (2 * bp)];
             const double* ct = &h_partial_[3 * (2 * bp + 1)];
             for (int r = 0; r < 3; ++r) {
@@ -949,6 +972,65 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
     return worst;
 }
 
+// The report stage of the batch the loop just ran (report.hpp, k_report.hip), queued on the
+// call's stream; run_loop's synchronisation follows.  Everything the loop's results are read
+// from has been copied by then; the stage rewrites PairDev (phase, pose, iteration) and runs
+// the loop's own R3 search once more, for every pair at once, at the final poses.
+int Engine::queue_report(int npairs, const int64_t* ns, const ReportReq& rq, hipStream_t s) {
+    const se3icp_report_options& o = *rq.opts;
+    if (!ensure<double>(d_rep_partial_, (size_t)nwork_ * kRepVals) || !ensure<double>(d_rep_out_, (size_t)npairs * kRepVals) ||
+        pinned(h_rep_, h_rep_cap_, (size_t)npairs * kRepVals))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    ReportArgs a{};
+    a.state = (const PairState*)d_state_.p;
+    a.hist = (double*)d_hist_.p;
+    a.max_d = o.max_correspondence_distance;
+    a.all_inliers = report_all_inliers(o.max_correspondence_distance) ? 1 : 0;
+    a.partial = (double*)d_rep_partial_.p;
+    a.out = (double*)d_rep_out_.p;
+    a.pair_wb = (const int32_t*)d_wb_.p;
+    a.pair_wn = (const int32_t*)d_wn_.p;
+    int64_t total = 0;
+    if (o.corr_idx || o.corr_dist) {  // compact per pair: pair p at the prefix sum of n_src
+        h_rep_off_.resize(npairs);
+        for (int p = 0; p < npairs; ++p) {
+            h_rep_off_[p] = total;
+            total += ns[p];
+        }
+        if (!ensure<int64_t>(d_rep_off_, npairs)) return SE3ICP_ERR_OUT_OF_MEMORY;
+        HIPCHK(hipMemcpyAsync(d_rep_off_.p, h_rep_off_.data(), sizeof(int64_t) * npairs, hipMemcpyHostToDevice, s));
+        a.out_off = (const int64_t*)d_rep_off_.p;
+        if (o.outputs_on_device) {
+            a.out_idx = o.corr_idx;
+            a.out_dist = o.corr_dist;
+        } else {
+            if ((o.corr_idx && !ensure<int32_t>(d_rep_idx_, (size_t)total)) ||
+                (o.corr_dist && !ensure<double>(d_rep_dist_, (size_t)total)))
+                return SE3ICP_ERR_OUT_OF_MEMORY;
+            a.out_idx = o.corr_idx ? (int32_t*)d_rep_idx_.p : nullptr;
+            a.out_dist = o.corr_dist ? (double*)d_rep_dist_.p : nullptr;
+        }
+    }
+    // what k_reduce_final clears for the next k_nn_prep (the single-query lists' counts and
+    // the searches' cost-class counts): the loop's last k_reduce_final did, cleared here too
+    HIPCHK(hipMemsetAsync(d_flag_count_.p, 0, 3 * sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(d_cls_.p, 0, sizeof(int32_t) * 2 * 8 * 16, s));
+    const View v = view();
+    launch_report_open(v, a, s);
+    launch_nn_prep(v, nullptr, s);
+    launch_nn(v, 3, s);
+    launch_report(v, a, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_rep_, d_rep_out_.p, sizeof(double) * kRepVals * npairs, hipMemcpyDeviceToHost, s));
+    if (!o.outputs_on_device) {
+        if (o.corr_idx)
+            HIPCHK(hipMemcpyAsync(o.corr_idx, d_rep_idx_.p, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost, s));
+        if (o.corr_dist)
+            HIPCHK(hipMemcpyAsync(o.corr_dist, d_rep_dist_.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
+    }
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- parameter sweep
 // One shared setup over the base clouds with alpha = beta = 1 (the stored rows are the raw
 // frame and the raw normalized point: 1.0 * x is exact), then the variants in groups: each
@@ -958,7 +1040,8 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
 // so every result equals that of register_batch with its variant.
 int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, const double* const* tgt,
                            const int64_t* nt, bool on_device, int method, int nvariants,
-                           const se3icp_params* variants, int max_group, se3icp_result* out, hipStream_t user_stream) {
+                           const se3icp_params* variants, int max_group, se3icp_result* out, hipStream_t user_stream,
+                           const se3icp_report_options* ropts, se3icp_report* reports) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
     se3icp_trace* tr = trace_;  // one-shot: the record covers this sweep only
     trace_ = nullptr;
@@ -1120,7 +1203,9 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
             gtr.pair = tr->pair - v0 * P;
             use = &gtr;
         }
-        rc = run_loop(g * P, vns.data(), mi.kind, mi.est, variants + v0, P, true, use, out + (size_t)v0 * P, s);
+        const ReportReq rq{ropts, reports ? reports + (size_t)v0 * P : nullptr};
+        rc = run_loop(g * P, vns.data(), mi.kind, mi.est, variants + v0, P, true, use, out + (size_t)v0 * P, s,
+                      (ropts && reports) ? &rq : nullptr);
         if (use) tr->iters_recorded = gtr.iters_recorded;
         if (rc && rc != SE3ICP_ERR_NONFINITE) return rc;
         if (rc) worst = rc;

@@ -58,12 +58,14 @@ class Engine {
 
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
                        const int64_t* nt, bool on_device, int method, const se3icp_params& prm,
-                       se3icp_result* out, hipStream_t user_stream);
+                       se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts = nullptr,
+                       se3icp_report* reports = nullptr);
     // Every pair under every parameter set of `variants`, results[v * npairs + p], with one
     // shared setup (sweep.hpp); the caller has validated the arguments (capi.cpp).
     int register_sweep(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
                        const int64_t* nt, bool on_device, int method, int nvariants, const se3icp_params* variants,
-                       int max_group, se3icp_result* out, hipStream_t user_stream);
+                       int max_group, se3icp_result* out, hipStream_t user_stream,
+                       const se3icp_report_options* ropts = nullptr, se3icp_report* reports = nullptr);
 
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
@@ -102,8 +104,16 @@ class Engine {
     // q % pairs_per_variant).  sweep: the setup time is the shared setup's (events 12 -> 8)
     // plus the group's (9 -> 13) instead of 12 -> 13.
     int prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipStream_t s);
+    // rq (may be null): the registration report of every pair, evaluated after the loop
+    struct ReportReq {
+        const se3icp_report_options* opts;  // (validated by the caller)
+        se3icp_report* out;                 // [npairs]
+    };
     int run_loop(int npairs, const int64_t* ns, int kind, int est, const se3icp_params* vprm, int pairs_per_variant,
-                 bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s);
+                 bool sweep, se3icp_trace* tr, se3icp_result* out, hipStream_t s, const ReportReq* rq = nullptr);
+    // queue the report stage behind the loop (k_report.hip): an R3 search at the final poses,
+    // the per-pair sums into h_rep_, the per-point outputs into the caller's buffers
+    int queue_report(int npairs, const int64_t* ns, const ReportReq& rq, hipStream_t s);
     std::vector<DevBuf*> all_bufs();
     int read_lrf_stats();
     int sync_stream(hipStream_t s);
@@ -148,7 +158,8 @@ class Engine {
         d_sqlist_, d_state_, d_trim_cand_, d_trim_ctr_, d_scales_, d_trim_hist_,
         d_lrf_fb_, d_lrf_fbn_,  // k_lrf8 -> exact k_lrf hand-over list and its count
         d_big_d_, d_big_i_,     // k_knn_big candidate buffers (neighbourhoods over kSmallK)
-        d_raw_, d_sweep_w_;     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
+        d_raw_, d_sweep_w_,     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
+        d_rep_partial_, d_rep_out_, d_rep_off_, d_rep_idx_, d_rep_dist_;  // the report's sums and per-point staging
     TreeBufs t3_, t12_;
     // pinned host mirrors
     PairDev* h_pairs_ = nullptr;
@@ -156,6 +167,9 @@ class Engine {
     double* h_partial_ = nullptr;
     int32_t* h_rechecked_ = nullptr;
     double* h_hist_ = nullptr;  // one pose-history row (npairs x 12)
+    double* h_rep_ = nullptr;   // the report's sums (npairs x kRepVals)
+    size_t h_rep_cap_ = 0;
+    std::vector<int64_t> h_rep_off_;  // first per-point output entry of each pair
     size_t h_pairs_cap_ = 0, h_red_cap_ = 0, h_partial_cap_ = 0, h_rechecked_cap_ = 0, h_hist_cap_ = 0;
     PairState* h_state_ = nullptr;  // loop state of every pair (read back after the loop)
     // [kLoopRing][npairs] each pair's phase in the next iteration, written by k_reduce_final

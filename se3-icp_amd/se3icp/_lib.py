@@ -35,6 +35,9 @@ EXPORTED_SYMBOLS = [
     "se3icp_get_result",
     "se3icp_register_batch", "se3icp_register_batch_device", "se3icp_register",
     "se3icp_register_sweep", "se3icp_register_sweep_device",
+    "se3icp_report_version", "se3icp_register_batch_report", "se3icp_register_batch_report_device",
+    "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
+    "se3icp_request_report", "se3icp_get_report",
     "se3icp_toldi_frames", "se3icp_knn_self", "se3icp_estimate_normals", "se3icp_nn",
     "se3icp_synthetic_pairs", "se3icp_synthetic_reference", "se3icp_synthetic_reference_device",
     "se3icp_random_downsample",
@@ -76,6 +79,38 @@ class Result(C.Structure):
         ("time_loop_ms", C.c_double),
         ("time_se3_correspondence_search_ms", C.c_double),
         ("time_before_pure_icp_ms", C.c_double),
+    ]
+
+
+STOP_CONVERGED = 0
+STOP_MAX_ITERATIONS = 1
+STOP_MAX_SE3_ITERATIONS = 2
+STOP_RUNAWAY = 3
+STOP_REASONS = ["converged", "max_iterations", "max_se3_iterations", "runaway"]
+
+
+class ReportOptions(C.Structure):
+    """se3icp_report_options; the per-point buffers are addresses (host or device)."""
+    _fields_ = [
+        ("max_correspondence_distance", C.c_double),
+        ("corr_idx", C.c_void_p),
+        ("corr_dist", C.c_void_p),
+        ("outputs_on_device", C.c_int32),
+        ("_reserved", C.c_int32),
+    ]
+
+
+class Report(C.Structure):
+    """se3icp_report."""
+    _fields_ = [
+        ("fitness", C.c_double),
+        ("inlier_rmse", C.c_double),
+        ("information", C.c_double * 36),
+        ("final_mse", C.c_double),
+        ("final_mse_change", C.c_double),
+        ("n_inliers", C.c_int64),
+        ("switched", C.c_int32),
+        ("stop_reason", C.c_int32),
     ]
 
 
@@ -144,6 +179,14 @@ def load():
     L.se3icp_register_sweep_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), vp,
                                                C.POINTER(C.c_int64), C.c_int, C.c_int32, C.POINTER(Params), C.c_int32,
                                                C.POINTER(Result), vp]
+    rop, rep = C.POINTER(ReportOptions), C.POINTER(Report)
+    L.se3icp_report_version.restype = C.c_int
+    L.se3icp_register_batch_report.argtypes = L.se3icp_register_batch.argtypes + [rop, rep]
+    L.se3icp_register_batch_report_device.argtypes = L.se3icp_register_batch_device.argtypes + [rop, rep]
+    L.se3icp_register_sweep_report.argtypes = L.se3icp_register_sweep.argtypes + [rop, rep]
+    L.se3icp_register_sweep_report_device.argtypes = L.se3icp_register_sweep_device.argtypes + [rop, rep]
+    L.se3icp_request_report.argtypes = [vp, rop]
+    L.se3icp_get_report.argtypes = [vp, rep]
     L.se3icp_register.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(Params),
                                   C.POINTER(Result)]
     L.se3icp_toldi_frames.argtypes = [C.c_int, dp, C.c_int64, C.c_int, dp]

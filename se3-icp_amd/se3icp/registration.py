@@ -84,6 +84,7 @@ class IterativeSE3Registration:
     def setSourceCloud(self, cloud):
         pts = read_ply_xyz(cloud) if isinstance(cloud, (str, bytes)) else _as_xyz(cloud)
         _lib.check(self._L.se3icp_set_source_cloud(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)), pts.shape[0]))
+        object.__setattr__(self, "_nsrc", getattr(self, "_nsrc", 0) + pts.shape[0])
 
     def setTargetCloud(self, cloud):
         pts = read_ply_xyz(cloud) if isinstance(cloud, (str, bytes)) else _as_xyz(cloud)
@@ -114,6 +115,26 @@ class IterativeSE3Registration:
         """SE(3) correspondences only, never switching to R3 (ISR.cpp:962-1127)."""
         # the C-ABI prints the reference's "pure se3 finished" (ISR.cpp:1127)
         return self._finish(self._L.se3icp_run_se3_pure(self._h, variant_name.encode()))
+
+    # ---- registration report (not in the reference: Open3D's RegistrationResult at the final pose)
+    def request_report(self, max_correspondence_distance: float = 0.0, per_point: bool = False):
+        """Ask the next run_* for a report (``.report``).  per_point: also the final match and
+        distance of every source point; call after the source cloud is set."""
+        n = getattr(self, "_nsrc", 0)
+        idx = np.full(n, -1, np.int32) if per_point else None
+        dist = np.zeros(n) if per_point else None
+        object.__setattr__(self, "_rep_bufs", (idx, dist))  # kept alive until the run has written them
+        opts = _lib.ReportOptions(float(max_correspondence_distance), idx.ctypes.data if per_point else None,
+                                  dist.ctypes.data if per_point else None, 0, 0)
+        _lib.check(self._L.se3icp_request_report(self._h, C.byref(opts)), "request_report")
+
+    @property
+    def report(self):
+        """The PairReport of the last run; Se3IcpError (invalid argument) when none was requested."""
+        rep = _lib.Report()
+        _lib.check(self._L.se3icp_get_report(self._h, C.byref(rep)), "get_report")
+        idx, dist = getattr(self, "_rep_bufs", (None, None))
+        return _report(rep, idx, dist)
 
     # ---- results (ISR.hpp:92-98)
     @property
@@ -491,6 +512,142 @@ def register_sweep_traced(pairs, method: str, variants, variant: int = 0, pair: 
         L.se3icp_set_trace(device, None)
     n = int(t.iters_recorded)
     return res, {k: v[:n] for k, v in tr.items()}
+
+
+# ---- registration reports (fitness, RMSE, information matrix and final matches per pair)
+@dataclass
+class PairReport:
+    fitness: float
+    inlier_rmse: float
+    information: np.ndarray          # (6, 6), rotation first
+    final_mse: float
+    final_mse_change: float
+    n_inliers: int
+    switched: int
+    stop_reason: int                 # _lib.STOP_*
+    corr_idx: np.ndarray | None = None   # (n_src,) int32: the final match of every source point
+    corr_dist: np.ndarray | None = None  # (n_src,) its distance, caller's units
+
+    @property
+    def stop_reason_name(self) -> str:
+        return _lib.STOP_REASONS[self.stop_reason]
+
+
+def _report(r, idx=None, dist=None) -> PairReport:
+    return PairReport(float(r.fitness), float(r.inlier_rmse), np.array(r.information).reshape(6, 6), float(r.final_mse),
+                      float(r.final_mse_change), int(r.n_inliers), int(r.switched), int(r.stop_reason), idx, dist)
+
+
+def _report_options(max_correspondence_distance: float, idx_ptr=None, dist_ptr=None, on_device=False):
+    return _lib.ReportOptions(float(max_correspondence_distance), idx_ptr, dist_ptr, 1 if on_device else 0, 0)
+
+
+def _split(arr, counts):
+    out, at = [], 0
+    for n in counts:
+        out.append(arr[at:at + n])
+        at += n
+    return out
+
+
+def register_batch_report(pairs, method: str, params: _lib.Params | None = None, device: int = 0,
+                          max_correspondence_distance: float = 0.0, per_point: bool = False):
+    """register_batch plus a PairReport per pair, evaluated at the final pose: returns
+    (results, reports); the results are bitwise register_batch's.  A distance <= 0 or inf makes
+    every point an inlier.  per_point: also the final match and its distance of every source
+    point (PairReport.corr_idx / corr_dist)."""
+    L = _lib.load()
+    srcs = [_as_xyz(s) for s, _ in pairs]
+    tgts = [_as_xyz(t) for _, t in pairs]
+    n = len(pairs)
+    dp = C.POINTER(C.c_double)
+    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
+    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
+    counts = [a.shape[0] for a in srcs]
+    ns = (C.c_int64 * n)(*counts)
+    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
+    res = (_lib.Result * n)()
+    rep = (_lib.Report * n)()
+    idx = np.full(sum(counts), -1, np.int32) if per_point else None
+    dist = np.zeros(sum(counts)) if per_point else None
+    opts = _report_options(max_correspondence_distance, idx.ctypes.data if per_point else None,
+                           dist.ctypes.data if per_point else None)
+    rc = L.se3icp_register_batch_report(device, n, sp, ns, tp, nt, _lib.method_id(method),
+                                        C.byref(params or _lib.default_params()), res, C.byref(opts), rep)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_batch_report")
+    ii = _split(idx, counts) if per_point else [None] * n
+    dd = _split(dist, counts) if per_point else [None] * n
+    return _results(res, n), [_report(rep[i], ii[i], dd[i]) for i in range(n)]
+
+
+def register_batch_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str,
+                                 params: _lib.Params | None = None, device: int = 0, stream: int = 0,
+                                 max_correspondence_distance: float = 0.0, corr_idx_ptr: int = 0,
+                                 corr_dist_ptr: int = 0, outputs_on_device: bool = True):
+    """register_batch_device plus reports: returns (results, reports).  corr_idx_ptr /
+    corr_dist_ptr: optional addresses of int32 / float64 buffers of sum(n_src) entries (pair p
+    at src_off[p] - src_off[0]) that receive the final matches -- device addresses (e.g.
+    ``torch_tensor.data_ptr()``) when outputs_on_device, host addresses otherwise."""
+    L = _lib.load()
+    n = len(src_off) - 1
+    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
+    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
+    res = (_lib.Result * n)()
+    rep = (_lib.Report * n)()
+    opts = _report_options(max_correspondence_distance, corr_idx_ptr or None, corr_dist_ptr or None, outputs_on_device)
+    rc = L.se3icp_register_batch_report_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
+                                               _lib.method_id(method), C.byref(params or _lib.default_params()), res,
+                                               C.c_void_p(stream) if stream else None, C.byref(opts), rep)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_batch_report_device")
+    return _results(res, n), [_report(rep[i]) for i in range(n)]
+
+
+def _sweep_reports(rep, nv, n):
+    return [[_report(rep[v * n + p]) for p in range(n)] for v in range(nv)]
+
+
+def register_sweep_report(pairs, method: str, variants, device: int = 0, max_group: int = 0,
+                          max_correspondence_distance: float = 0.0):
+    """register_sweep plus reports: returns (results[v][p], reports[v][p]), e.g. to pick the
+    alpha_rot of a sweep by fitness where there is no ground truth."""
+    L = _lib.load()
+    srcs = [_as_xyz(s) for s, _ in pairs]
+    tgts = [_as_xyz(t) for _, t in pairs]
+    n, nv = len(pairs), len(variants)
+    dp = C.POINTER(C.c_double)
+    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
+    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
+    ns = (C.c_int64 * n)(*[a.shape[0] for a in srcs])
+    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
+    res = (_lib.Result * max(1, nv * n))()
+    rep = (_lib.Report * max(1, nv * n))()
+    opts = _report_options(max_correspondence_distance)
+    rc = L.se3icp_register_sweep_report(device, n, sp, ns, tp, nt, _lib.method_id(method), nv,
+                                        _variant_array(variants) if nv else None, max_group, res, C.byref(opts), rep)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_sweep_report")
+    return _sweep_results(res, nv, n), _sweep_reports(rep, nv, n)
+
+
+def register_sweep_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str, variants, device: int = 0,
+                                 stream: int = 0, max_group: int = 0, max_correspondence_distance: float = 0.0):
+    """register_sweep_report for clouds already in HBM."""
+    L = _lib.load()
+    n, nv = len(src_off) - 1, len(variants)
+    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
+    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
+    res = (_lib.Result * max(1, nv * n))()
+    rep = (_lib.Report * max(1, nv * n))()
+    opts = _report_options(max_correspondence_distance)
+    rc = L.se3icp_register_sweep_report_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
+                                               _lib.method_id(method), nv, _variant_array(variants) if nv else None,
+                                               max_group, res, C.c_void_p(stream) if stream else None,
+                                               C.byref(opts), rep)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_sweep_report_device")
+    return _sweep_results(res, nv, n), _sweep_reports(rep, nv, n)
 
 
 # ---- stage entry points (one per reference function on the hot path)

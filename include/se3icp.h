@@ -194,6 +194,66 @@ int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_sr
                                  const se3icp_params* variants, int32_t max_group, se3icp_result* results,
                                  void* hip_stream);
 
+/* ------------------------------------------------------------- cloud graphs
+ * What the reference's drivers actually hand over: a set of scans and the pairs to register
+ * among them (examples/benchmark_kitti.cpp:101-131 registers scan i+1 onto scan i, so every
+ * interior scan is the target of one pair and the source of the next); likewise scans
+ * localised against one map, or the loop-closure edges of a pose graph.
+ *
+ * n_clouds distinct clouds; pair p registers clouds[src_cloud[p]] onto clouds[tgt_cloud[p]].
+ * results[p] is bitwise what se3icp_register_batch returns for that pair (T, both iteration
+ * counts, status, scaling_factor; not the times, not num_rechecked).
+ * A self edge (src == tgt), a repeated edge, a cloud no edge uses (never read, may be empty)
+ * and any edge order are valid.
+ * sharing: 0 engine's choice (= 3); 1 upload / ingest / centroid / radius once per cloud;
+ * 2 also one neighbour selection (exact kNN, TOLDI frames, normals: the bulk of the setup) per
+ * (cloud, normalization) class -- the uses of a cloud whose pairs give it the same scale
+ * (run_se3_*: scale_preprocessing / max(r_src, r_tgt)); for pt2pt / pt2pl / gicp, which keep
+ * raw coordinates, one per cloud; 3 reserved for neighbour-set adoption between the classes
+ * of one cloud, which is not built: it behaves as 2.  Every level returns the same bits.
+ * The saving is upload and setup compute, NOT memory: the loop's state lives at a use's own
+ * slots, so each of the 2 * n_pairs uses is materialised (normalized copy and 3-D kd-tree of
+ * its own), and the distinct clouds' raw coordinates are held beside them.  Planning the
+ * classes needs the clouds' centroids and radii on the host: one synchronisation more than a
+ * batch.
+ * Arguments are checked before the device is looked up: SE3ICP_ERR_INVALID_ARG for
+ * n_clouds <= 0, n_pairs <= 0, NULL arrays, an index outside [0, n_clouds), sharing outside
+ * 0..3; SE3ICP_ERR_INVALID_METHOD; SE3ICP_ERR_EMPTY_CLOUD for an empty cloud some edge uses;
+ * without a device SE3ICP_ERR_NO_DEVICE, never a CPU fallback.
+ * se3icp_set_trace before the call: trace.pair is the edge index.  se3icp_set_lrf_exact
+ * applies to every class.  se3icp_last_kernel_times(_n): the setup entries (lrf_*) are the
+ * classes' one selection each; setup_ms spans upload to the loop's start. */
+int se3icp_register_graph(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                          int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                          const se3icp_params* params, int32_t sharing, se3icp_result* results);
+/* Same, with the clouds resident in HBM: d_xyz is the concatenation of every cloud's AoS xyz,
+ * off (n_clouds + 1 host entries) each cloud's point range (see se3icp_register_batch_device
+ * for hip_stream). */
+int se3icp_register_graph_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                 int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                                 const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                 void* hip_stream);
+/* The same plus a report per edge (registration reports, below); the per-point buffers of
+ * opts are laid out per edge at the prefix sum of the edges' n_src, as for a batch. */
+struct se3icp_report_options;
+struct se3icp_report;
+int se3icp_register_graph_report(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                                 int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                                 const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                 const struct se3icp_report_options* opts, struct se3icp_report* reports);
+int se3icp_register_graph_report_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                        int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud,
+                                        int method, const se3icp_params* params, int32_t sharing,
+                                        se3icp_result* results, void* hip_stream,
+                                        const struct se3icp_report_options* opts, struct se3icp_report* reports);
+/* Counters of the last graph call on `device`: out[SE3ICP_GRAPH_STATS_N], n >= that (else
+ * SE3ICP_ERR_INVALID_ARG) = {distinct clouds some edge uses, uses (2 * n_pairs), classes,
+ * classes that ran a full neighbour selection, queries adopted, queries rejected by order,
+ * queries rejected by gap, queries without a list (the last four: adoption, always 0),
+ * bytes uploaded}. */
+#define SE3ICP_GRAPH_STATS_N 9
+int se3icp_last_graph_stats(int device, int64_t* out, int n);
+
 /* ------------------------------------------------------------- registration reports
  * What says whether a pose is any good, evaluated at the FINAL pose as Open3D's
  * RegistrationResult and GetInformationMatrixFromPointClouds are.  For every source point i

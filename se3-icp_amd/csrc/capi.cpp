@@ -10,10 +10,13 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "graph.hpp"
 #include "se3icp.h"
 
 using se3icp::Engine;
 using se3icp::engine_for;
+using se3icp::graph_check;
+using se3icp::GS_COUNT;
 
 namespace {
 
@@ -308,6 +311,94 @@ int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const doubl
     std::lock_guard<std::mutex> lk(e->mutex());
     return e->register_sweep(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, n_variants, variants,
                              max_group, results, (hipStream_t)hip_stream, opts, reports);
+}
+
+// ------------------------------------------------------------------ cloud graphs
+// Checked before the device is looked up, as the sweeps' arguments are (graph.hpp).
+static int graph_run(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts, bool on_device,
+                     int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                     const se3icp_params* params, int32_t sharing, se3icp_result* results, void* hip_stream,
+                     bool with_report, const se3icp_report_options* opts, se3icp_report* reports) {
+    if (with_report) {
+        const int rc = report_check(opts, reports, true);
+        if (rc) return rc;
+    }
+    int rc = graph_check(n_clouds, n_pts, nullptr, n_pairs, src_cloud, tgt_cloud, method, SE3ICP_NUM_METHODS, sharing,
+                         results);
+    if (rc) return rc;
+    if (method >= SE3ICP_SE3_PT2PT && params && params->number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (!xyz[src_cloud[p]] || !xyz[tgt_cloud[p]]) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    se3icp_params p;
+    if (params) p = *params; else se3icp_default_params(&p);
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_graph(n_clouds, xyz, n_pts, n_pairs, src_cloud, tgt_cloud, on_device, method, p, sharing, results,
+                             (hipStream_t)hip_stream, with_report ? opts : nullptr, with_report ? reports : nullptr);
+}
+
+// the per-cloud pointers and sizes of clouds concatenated in HBM
+static int cloud_ranges(int32_t n_clouds, const double* d_xyz, const int64_t* off, std::vector<const double*>& x,
+                        std::vector<int64_t>& n) {
+    if (n_clouds <= 0 || !d_xyz || !off) return SE3ICP_ERR_INVALID_ARG;
+    x.resize(n_clouds);
+    n.resize(n_clouds);
+    for (int32_t c = 0; c < n_clouds; ++c) {
+        x[c] = d_xyz + 3 * off[c];
+        n[c] = off[c + 1] - off[c];
+    }
+    return SE3ICP_OK;
+}
+
+int se3icp_register_graph(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                          int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                          const se3icp_params* params, int32_t sharing, se3icp_result* results) {
+    if (!xyz) return SE3ICP_ERR_INVALID_ARG;
+    return graph_run(device, n_clouds, xyz, n_pts, false, n_pairs, src_cloud, tgt_cloud, method, params, sharing, results,
+                     nullptr, false, nullptr, nullptr);
+}
+
+int se3icp_register_graph_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                 int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                                 const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                 void* hip_stream) {
+    std::vector<const double*> x;
+    std::vector<int64_t> n;
+    const int rc = cloud_ranges(n_clouds, d_xyz, off, x, n);
+    if (rc) return rc;
+    return graph_run(device, n_clouds, x.data(), n.data(), true, n_pairs, src_cloud, tgt_cloud, method, params, sharing,
+                     results, hip_stream, false, nullptr, nullptr);
+}
+
+int se3icp_register_graph_report(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                                 int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                                 const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                 const se3icp_report_options* opts, se3icp_report* reports) {
+    if (!xyz) return SE3ICP_ERR_INVALID_ARG;
+    return graph_run(device, n_clouds, xyz, n_pts, false, n_pairs, src_cloud, tgt_cloud, method, params, sharing, results,
+                     nullptr, true, opts, reports);
+}
+
+int se3icp_register_graph_report_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                        int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
+                                        const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                        void* hip_stream, const se3icp_report_options* opts, se3icp_report* reports) {
+    std::vector<const double*> x;
+    std::vector<int64_t> n;
+    const int rc = cloud_ranges(n_clouds, d_xyz, off, x, n);
+    if (rc) return rc;
+    return graph_run(device, n_clouds, x.data(), n.data(), true, n_pairs, src_cloud, tgt_cloud, method, params, sharing,
+                     results, hip_stream, true, opts, reports);
+}
+
+int se3icp_last_graph_stats(int device, int64_t* out, int n) {
+    if (!out || n < GS_COUNT) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    for (int k = 0; k < GS_COUNT; ++k) out[k] = e->graph_stats()[k];
+    return SE3ICP_OK;
 }
 
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,

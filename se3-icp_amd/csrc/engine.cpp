@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 
+#include "graph.hpp"
 #include "report.hpp"
 #include "sweep.hpp"
 #include "tree.hpp"
@@ -105,6 +106,7 @@ hipError_t spin_phases(const volatile int32_t* slot, int n, hipStream_t s) {
     }
 }
 
+static_assert(GS_COUNT == 9, "Engine::graph_stats_");
 constexpr int kStatSlots = 64;  // work counters: [64][kStatCols] u64 (spread against atomic contention)
 
 }  // namespace
@@ -137,7 +139,8 @@ std::vector<DevBuf*> Engine::all_bufs() {
                      &d_rep_partial_, &d_rep_out_, &d_rep_off_, &d_rep_idx_, &d_rep_dist_,
                      &t3_.perm, &t3_.pos, &t3_.vec, &t3_.vec64, &t3_.vec64a, &t3_.blo, &t3_.bhi, &t3_.lo, &t3_.hi, &t3_.scr,
                      &t12_.perm, &t12_.pos, &t12_.vec, &t12_.vec64, &t12_.blo, &t12_.bhi, &t12_.lo, &t12_.hi, &t12_.scr,
-                     &t12_.vecT};
+                     &t12_.vecT,
+                     &g_raw_xyz_, &g_raw_conf_, &g_seg_, &g_chunks_};
 }
 
 Engine::~Engine() {
@@ -400,7 +403,22 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
     // 4) 3-D kd-trees of every cloud (kNN for TOLDI / normals, and the R3 NN of the loop)
     int rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
     if (rc) return rc;
-    v = view();
+    rc = setup_knn(s);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    // 5) 12-D kd-trees over the alpha/beta-weighted SE(3) elements
+    have12_ = build12;
+    if (build12) {
+        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);  // f64 source elements in tree order
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// kNN / TOLDI frames / normals of the clouds that were normalized and given their 3-D trees
+// (step 4 of setup_clouds; Engine::register_graph runs it over its classes).
+int Engine::setup_knn(hipStream_t s) {
+    const View v = view();
     bool any_knn = false;
     for (int c = 0; c < nclouds_; ++c) any_knn |= h_setup_[c].k_knn > 0;
     if (any_knn) {
@@ -438,7 +456,9 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
             // query of a cloud whose k it cannot hold) go to the exact kernels
             // waves aligned to each cloud's first point (results independent of the batch)
             std::vector<int32_t> wb(nclouds_ + 1, 0);
-            for (int c = 0; c < nclouds_; ++c) wb[c + 1] = wb[c] + (h_clouds_[c].n + 7) / 8;
+            // (a cloud that wants no neighbours gets no waves: the kernel's search for a wave's
+            // cloud takes the last one that starts at or before it)
+            for (int c = 0; c < nclouds_; ++c) wb[c + 1] = wb[c] + (h_setup_[c].k_knn > 0 ? (h_clouds_[c].n + 7) / 8 : 0);
             const int nw = wb[nclouds_];
             if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * nw + 64) || !ensure<int32_t>(d_lrf_fbn_, 2 + nclouds_ + 1))
                 return SE3ICP_ERR_OUT_OF_MEMORY;
@@ -458,13 +478,6 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
         HIPCHK(hipMemcpyAsync(h_lrf_stats_, d_stats_.p, sizeof(unsigned long long) * kStatCols * kStatSlots,
                               hipMemcpyDeviceToHost, s));
         lrf_stats_pending_ = true;
-    }
-    HIPCHK(hipGetLastError());
-    // 5) 12-D kd-trees over the alpha/beta-weighted SE(3) elements
-    have12_ = build12;
-    if (build12) {
-        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);  // f64 source elements in tree order
-        if (rc) return rc;
     }
     return 0;
 }
@@ -1213,6 +1226,277 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     // (ktimes_: the setup entries are the shared setup's, read at the first group's
     // synchronisation; the loop entries were summed over the groups)
     return worst;
+}
+
+// ----------------------------------------------------------------------------- cloud graphs
+// P edges over C distinct clouds (graph.hpp).  Two layouts follow one another in the same
+// buffers, both with the column stride of the larger (the 2P uses):
+//   A  the distinct clouds some edge uses: one upload, k_ingest, centroid, radius each; the
+//      centroids and radii go to the host (ONE extra synchronisation against a plain batch,
+//      whose normalization parameters never leave the device), which plans the classes;
+//   B  the 2P uses, as a batch lays them out: k_graph_normalize from A's raw columns and a 3-D
+//      tree for every use; kNN / frames / normals only for the first use of every class (the
+//      other uses ask for no neighbours, which the kernels skip); k_graph_share copies those
+//      to the class's other uses; then 12-D trees, prepare_pairs, setup_chunks and run_loop
+//      exactly as a batch.
+// A's raw columns are kept by swapping their buffer out for B's (memory is not saved: every
+// use is materialised, the loop's state lives at a use's slots).  A cloud sets up bitwise the
+// same at any position of any batch, so every result equals register_batch's for the expanded
+// pair list.
+int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts, int P, const int32_t* esrc,
+                           const int32_t* etgt, bool on_device, int method, const se3icp_params& prm, int sharing,
+                           se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
+                           se3icp_report* reports) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    se3icp_trace* tr = trace_;  // one-shot: the record covers this call only (trace.pair: the edge)
+    trace_ = nullptr;
+    if (C <= 0 || P <= 0 || !xyz || !npts || !esrc || !etgt || !out) return SE3ICP_ERR_INVALID_ARG;
+    if (tr && (tr->pair < 0 || tr->pair >= P || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
+    if (tr) tr->iters_recorded = 0;
+    MethodInfo mi;
+    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
+    if (sharing == 0) sharing = 3;
+    // (level 3, neighbour-set adoption between the classes of a cloud, is not built: as 2)
+    const bool se3 = mi.kind != KIND_ICP;
+    const int k_lrf = se3 ? prm.number_of_nn_for_LRF : 0;
+    if (se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
+    int k_nrm_s = 0, k_nrm_t = 0;
+    if (mi.est == EST_PT2PL) k_nrm_t = 30;
+    if (mi.est == EST_GICP) { k_nrm_s = 20; k_nrm_t = 20; }
+    const int kmax = std::max({k_lrf, k_nrm_s, k_nrm_t, 1});
+    for (int64_t& g : graph_stats_) g = 0;
+
+    // ---- layouts A (used clouds, in cloud order) and B (uses)
+    std::vector<int32_t> slotA(C, -1), cloudA;
+    for (int p = 0; p < P; ++p) {
+        if (esrc[p] < 0 || esrc[p] >= C || etgt[p] < 0 || etgt[p] >= C) return SE3ICP_ERR_INVALID_ARG;
+        slotA[esrc[p]] = slotA[etgt[p]] = 0;
+    }
+    for (int c = 0; c < C; ++c)
+        if (slotA[c] == 0) {
+            if (npts[c] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+            if (!xyz[c]) return SE3ICP_ERR_INVALID_ARG;
+            slotA[c] = (int32_t)cloudA.size();
+            cloudA.push_back(c);
+        }
+    const int CA = (int)cloudA.size();
+    std::vector<int64_t> ns(P), nt(P);
+    int64_t NA = 0, NU = 0;
+    int nchU = 0;
+    for (int a = 0; a < CA; ++a) NA += npts[cloudA[a]];
+    for (int p = 0; p < P; ++p) {
+        ns[p] = npts[esrc[p]];
+        nt[p] = npts[etgt[p]];
+        NU += ns[p] + nt[p];
+        nchU += (int)((ns[p] + kChunk - 1) / kChunk + (nt[p] + kChunk - 1) / kChunk);
+    }
+
+    HIPCHK(hipSetDevice(dev_));
+    hipStream_t s = user_stream ? user_stream : stream_;
+    ktimes_ = KernelTimes{};
+    HIPCHK(hipEventRecord(ev_[12], s));
+
+    // buffers of the larger layout first (NA <= NU points, and as many chunks at most)
+    int rc = alloc_points(NU, kmax);
+    if (rc) return rc;
+    const size_t L = (size_t)ld_;
+    if (!ensure<CloudDev>(d_clouds_, 2 * (size_t)P) || !ensure<CloudSetup>(d_setup_, 2 * (size_t)P) ||
+        !ensure<ChunkWork>(d_chunks_, nchU) || !ensure<const double*>(d_inptr_, CA) ||
+        !ensure<double>(d_partial_, (size_t)nchU * 9) || !ensure<double>(d_centers_, 6 * (size_t)P) ||
+        !ensure<double>(d_scales_, P) || !ensure<GraphSeg>(g_seg_, 2 * (size_t)P))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    if (pinned(h_partial_, h_partial_cap_, (size_t)nchU * 9 + 6 * (size_t)P + 8)) return SE3ICP_ERR_OUT_OF_MEMORY;
+
+    // ---- A: every used cloud once
+    npairs_ = 0;
+    nclouds_ = CA;
+    ntot_ = NA;
+    std::vector<CloudDev> clA(CA);
+    std::vector<CloudSetup> stA(CA, CloudSetup{});
+    std::vector<ChunkWork> chA;
+    std::vector<const double*> inA(CA, nullptr);
+    {
+        int64_t off = 0;
+        for (int a = 0; a < CA; ++a) {
+            const int64_t n = npts[cloudA[a]];
+            clA[a] = CloudDev{(int32_t)off, (int32_t)n};
+            stA[a].want_conf = mi.kind == KIND_CF;
+            stA[a].alpha = stA[a].beta = stA[a].norm_scale = 1.0;
+            for (int64_t p0 = 0; p0 < n; p0 += kChunk) chA.push_back(ChunkWork{a, (int32_t)p0});
+            if (on_device) {
+                inA[a] = xyz[cloudA[a]];
+            } else {
+                double* dst = (double*)d_in_.p + 3 * (size_t)off;
+                HIPCHK(hipMemcpyAsync(dst, xyz[cloudA[a]], sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
+                inA[a] = dst;
+                graph_stats_[GS_BYTES_UPLOADED] += (int64_t)sizeof(double) * 3 * n;
+            }
+            off += n;
+        }
+    }
+    const int nchA = (int)chA.size();
+    h_clouds_ = clA;
+    h_setup_ = stA;
+    HIPCHK(hipMemcpyAsync(d_clouds_.p, clA.data(), sizeof(CloudDev) * CA, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_setup_.p, stA.data(), sizeof(CloudSetup) * CA, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_chunks_.p, chA.data(), sizeof(ChunkWork) * nchA, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_inptr_.p, inA.data(), sizeof(double*) * CA, hipMemcpyHostToDevice, s));
+    View v = view();
+    launch_ingest(v, (const ChunkWork*)d_chunks_.p, nchA, (double*)d_partial_.p, s);
+    HIPCHK(hipGetLastError());
+    std::vector<double> cenC(3 * (size_t)C, 0.0), radC(C, 0.0);  // by the call's cloud index
+    if (se3) {
+        // GetCenter and the radius as a batch forms them (k_pair_centers folds a cloud's chunks by
+        // chunk index modulo 64, then a butterfly: the same sum at any position while a cloud's
+        // chunks are contiguous and in order; the radius is a maximum)
+        launch_pair_centers(v, (const ChunkWork*)d_chunks_.p, nchA, (const double*)d_partial_.p, (double*)d_centers_.p, s);
+        launch_radius(v, (const ChunkWork*)d_chunks_.p, nchA, (const double*)d_centers_.p, (double*)d_partial_.p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_partial_, d_centers_.p, sizeof(double) * 3 * CA, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_partial_ + 3 * (size_t)CA, d_partial_.p, sizeof(double) * nchA, hipMemcpyDeviceToHost, s));
+        SYNC_STREAM(s);
+        for (int a = 0; a < CA; ++a)
+            for (int x = 0; x < 3; ++x) cenC[3 * (size_t)cloudA[a] + x] = h_partial_[3 * (size_t)a + x];
+        for (int a = 0; a < CA; ++a) radC[cloudA[a]] = -1.0;
+        for (int k = 0; k < nchA; ++k) {
+            double& r = radC[cloudA[chA[k].cloud]];
+            r = std::fmax(r, h_partial_[3 * (size_t)CA + k]);
+        }
+    } else {
+        // run_icp: the centroid as setup_clouds forms it on the host (chunk sums in order)
+        HIPCHK(hipMemcpyAsync(h_partial_, d_partial_.p, sizeof(double) * 9 * nchA, hipMemcpyDeviceToHost, s));
+        SYNC_STREAM(s);
+        std::vector<double> sum(3 * (size_t)CA, 0.0);
+        for (int k = 0; k < nchA; ++k)
+            for (int x = 0; x < 3; ++x) sum[3 * (size_t)chA[k].cloud + x] += h_partial_[9 * (size_t)k + x];
+        for (int a = 0; a < CA; ++a)
+            for (int x = 0; x < 3; ++x) cenC[3 * (size_t)cloudA[a] + x] = sum[3 * (size_t)a + x] / (double)clA[a].n;
+    }
+
+    // ---- classes
+    GraphPlan plan;
+    graph_plan(P, esrc, etgt, se3, prm.scale_preprocessing, cenC.data(), radC.data(), k_nrm_s, k_nrm_t, sharing >= 2,
+               &plan);
+    const int K = (int)plan.classes.size();
+    graph_stats_[GS_CLOUDS] = CA;
+    graph_stats_[GS_USES] = 2 * (int64_t)P;
+    graph_stats_[GS_CLASSES] = K;
+
+    // ---- B: the uses.  A's raw columns and confidences are kept aside; every use is normalized
+    // from them and given its 3-D tree, the first use of a class ("home") runs the class's
+    // neighbour selection, frames and normals, and the other uses copy them.
+    auto regrow = [&](DevBuf& kept, DevBuf& cur, size_t bytes) {
+        std::swap(kept, cur);
+        return ensure<char>(cur, bytes) != nullptr;
+    };
+    if (!regrow(g_raw_xyz_, d_xyz64_, sizeof(double) * 3 * L) || !regrow(g_raw_conf_, d_conf64_, sizeof(double) * L))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    nclouds_ = 2 * P;
+    npairs_ = P;
+    ntot_ = NU;
+    std::vector<int32_t> home(K, -1);  // first use of each class
+    for (int u = 0; u < 2 * P; ++u)
+        if (home[plan.use_class[u]] < 0) home[plan.use_class[u]] = u;
+    std::vector<CloudDev> clU(2 * (size_t)P);
+    std::vector<CloudSetup> stU(2 * (size_t)P), stRun(2 * (size_t)P);  // a batch's table / the setup's
+    std::vector<ChunkWork> chU, chShare;
+    std::vector<GraphSeg> segU(2 * (size_t)P), segShare(2 * (size_t)P);
+    std::vector<double> cenU(6 * (size_t)P), scaleU(P, 1.0);
+    int max_n = 1;
+    {
+        int64_t off = 0;
+        for (int u = 0; u < 2 * P; ++u) {
+            const int side = u & 1;
+            const GraphClass& gc = plan.classes[plan.use_class[u]];
+            const int64_t n = npts[gc.cloud];
+            clU[u] = CloudDev{(int32_t)off, (int32_t)n};
+            CloudSetup& st = stU[u];
+            st = CloudSetup{};
+            st.k_lrf = k_lrf;
+            st.k_nrm = side == 0 ? k_nrm_s : k_nrm_t;
+            st.k_knn = std::max(st.k_lrf, st.k_nrm);
+            st.want_cov = mi.est == EST_GICP;
+            st.want_conf = mi.kind == KIND_CF;
+            st.is_target = side;
+            st.cf_target = (mi.kind == KIND_CF && side == 1) ? 1 : 0;
+            st.alpha = prm.alpha_rot;
+            st.beta = prm.beta_transl;
+            for (int x = 0; x < 3; ++x) {
+                st.norm_center[x] = gc.norm_center[x];
+                st.f32_center[x] = gc.f32_center[x];
+                cenU[3 * (size_t)u + x] = gc.norm_center[x];
+            }
+            st.norm_scale = gc.norm_scale;
+            if (side == 0) scaleU[u >> 1] = gc.norm_scale;
+            segU[u] = GraphSeg{clA[slotA[gc.cloud]].off, slotA[gc.cloud], 0, 0};
+            for (int64_t p0 = 0; p0 < n; p0 += kChunk) chU.push_back(ChunkWork{u, (int32_t)p0});
+            max_n = std::max<int>(max_n, (int)n);
+            off += n;
+        }
+        for (int u = 0; u < 2 * P; ++u) {
+            const int k = plan.use_class[u];
+            const GraphClass& gc = plan.classes[k];
+            // the setup's table: a home use selects for its class (the largest normals k of the
+            // class's uses; none where another class of the cloud owns the normals), the others
+            // select nothing
+            CloudSetup& st = stRun[u];
+            st = stU[u];
+            const bool is_home = home[k] == u;
+            st.k_lrf = is_home ? k_lrf : 0;
+            st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
+            st.k_knn = std::max(st.k_lrf, st.k_nrm);
+            graph_stats_[GS_FULL] += st.k_knn > 0;
+            const int hf = home[k], hn = home[gc.nrm_from];  // where its frames / normals are computed
+            segShare[u] = GraphSeg{clU[hf].off, hf, clU[hn].off, (hf != u && se3) ? 1 : 0};
+            if ((hf != u && se3) || hn != u)
+                for (int64_t p0 = 0; p0 < clU[u].n; p0 += kChunk) chShare.push_back(ChunkWork{u, (int32_t)p0});
+        }
+    }
+    tree_L_ = tree_depth_for(max_n);
+    h_clouds_ = clU;
+    h_setup_ = stRun;
+    const int nchU2 = (int)chU.size(), nchS = (int)chShare.size();
+    if (!ensure<ChunkWork>(g_chunks_, nchS)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    HIPCHK(hipMemcpyAsync(d_clouds_.p, clU.data(), sizeof(CloudDev) * 2 * P, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_setup_.p, stRun.data(), sizeof(CloudSetup) * 2 * P, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_chunks_.p, chU.data(), sizeof(ChunkWork) * nchU2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g_seg_.p, segU.data(), sizeof(GraphSeg) * 2 * P, hipMemcpyHostToDevice, s));
+    if (se3) {
+        HIPCHK(hipMemcpyAsync(d_centers_.p, cenU.data(), sizeof(double) * 6 * P, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_scales_.p, scaleU.data(), sizeof(double) * P, hipMemcpyHostToDevice, s));
+    }
+    launch_graph_normalize(view(), (const ChunkWork*)d_chunks_.p, nchU2, (const GraphSeg*)g_seg_.p,
+                           (const double*)g_raw_xyz_.p, (const double*)g_raw_conf_.p, s);
+    HIPCHK(hipGetLastError());
+    rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+    if (rc) return rc;
+    rc = setup_knn(s);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    // the batch's own table from here on (the copies below read cf_target of the use itself)
+    h_setup_ = stU;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, stU.data(), sizeof(CloudSetup) * 2 * P, hipMemcpyHostToDevice, s));
+    if (nchS > 0) {
+        HIPCHK(hipMemcpyAsync(g_chunks_.p, chShare.data(), sizeof(ChunkWork) * nchS, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g_seg_.p, segShare.data(), sizeof(GraphSeg) * 2 * P, hipMemcpyHostToDevice, s));
+        launch_graph_share(view(), (const ChunkWork*)g_chunks_.p, nchS, (const GraphSeg*)g_seg_.p, s);
+        HIPCHK(hipGetLastError());
+    }
+    have12_ = se3;
+    if (se3) {
+        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
+        if (rc) return rc;
+    }
+    rc = prepare_pairs(P, ns.data(), nt.data(), s);
+    if (rc) return rc;
+    rc = setup_chunks(P, s);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * ld_, s));  // no previous match yet
+    HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
+    for (double& t : trace_prev_) t = 0;
+    HIPCHK(hipEventRecord(ev_[13], s));
+    const ReportReq rq{ropts, reports};
+    return run_loop(P, ns.data(), mi.kind, mi.est, &prm, P, false, tr, out, s, (ropts && reports) ? &rq : nullptr);
 }
 
 // Row it-1 of the armed trace after iteration `it` completed (the stream is idle: the

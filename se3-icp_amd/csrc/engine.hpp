@@ -67,6 +67,16 @@ class Engine {
                        int max_group, se3icp_result* out, hipStream_t user_stream,
                        const se3icp_report_options* ropts = nullptr, se3icp_report* reports = nullptr);
 
+    // Edge p registers clouds[src[p]] onto clouds[tgt[p]]; every distinct cloud is uploaded and
+    // ingested once and every (cloud, normalization) class selects its neighbours once
+    // (graph.hpp); results[p] is bitwise register_batch's for that pair.  The caller has
+    // validated the arguments.
+    int register_graph(int nclouds, const double* const* xyz, const int64_t* npts, int npairs, const int32_t* src,
+                       const int32_t* tgt, bool on_device, int method, const se3icp_params& prm, int sharing,
+                       se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts = nullptr,
+                       se3icp_report* reports = nullptr);
+    const int64_t* graph_stats() const { return graph_stats_; }  // [GS_COUNT] of the last register_graph
+
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
     int toldi_frames(const double* xyz, int64_t n, int k, double* frames);
@@ -95,6 +105,8 @@ class Engine {
     // together with the reference's preprocessing and scale[p] receives the factor.
     int setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool normalize_pairs, double scale_pre,
                      bool build12, std::vector<double>* centers, std::vector<double>* scales, hipStream_t s);
+    // kNN / frames / normals of the clouds set up so far (step 4 of setup_clouds)
+    int setup_knn(hipStream_t s);
     int setup_chunks(int npairs, hipStream_t s);
     // the two halves of a registration around setup_clouds.  prepare_pairs: the work table
     // of k_reduce and the per-pair buffers of a batch of npairs pairs laid out src 0, tgt 0,
@@ -161,6 +173,10 @@ class Engine {
         d_raw_, d_sweep_w_,     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
         d_rep_partial_, d_rep_out_, d_rep_off_, d_rep_idx_, d_rep_dist_;  // the report's sums and per-point staging
     TreeBufs t3_, t12_;
+    // register_graph: the distinct clouds' raw columns and confidences (swapped with xyz64 /
+    // conf64 between the call's two layouts), the segment and chunk tables of the k_graph kernels
+    DevBuf g_raw_xyz_, g_raw_conf_, g_seg_, g_chunks_;
+    int64_t graph_stats_[9] = {};
     // pinned host mirrors
     PairDev* h_pairs_ = nullptr;
     double* h_red_ = nullptr;

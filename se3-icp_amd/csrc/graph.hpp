@@ -1,0 +1,163 @@
+// graph.hpp — host-side planning of a registration over a shared cloud set
+// (Engine::register_graph) and the launchers of k_graph.hip.
+//
+// A graph call names C distinct clouds and P edges; edge p registers cloud src[p] onto cloud
+// tgt[p].  The loop understands a batch of 2P "use" clouds laid out src 0, tgt 0, src 1, ...
+// (use 2p + side), so a cloud that several edges name is materialised once per use -- the
+// saving is upload and setup compute, not memory.  What the uses of a cloud can share depends
+// on how the edge normalizes it (ISR.cpp:568-582): every use has the cloud's own centroid, but
+// the scale is the pair's, scale_pre * (1 / max(r_src, r_tgt)), and the vanilla methods centre
+// their f32 copy on the pair's target.  A CLASS is a cloud under one such normalization:
+// (cloud, bits of norm_scale, bits of f32_center).  Uses of one class are bitwise the same
+// cloud to every setup kernel, so the class's neighbour selection, frames and normals -- the
+// bulk of the setup -- run once, at its first use, and are copied to the others.
+// This header holds the plan, which needs no device.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <vector>
+
+namespace se3icp {
+
+// sharing levels of se3icp_register_graph
+constexpr int kGraphSharingMin = 0, kGraphSharingMax = 3;
+// se3icp_last_graph_stats
+enum GraphStat : int {
+    GS_CLOUDS = 0,      // distinct clouds some edge uses
+    GS_USES,            // 2 * edges
+    GS_CLASSES,
+    GS_FULL,            // classes that ran a full neighbour selection
+    GS_ADOPTED,         // queries whose neighbour set was adopted from another class
+    GS_REJ_ORDER,       // ... rejected by the order check
+    GS_REJ_GAP,         // ... rejected by the gap check
+    GS_NO_LIST,         // ... without a list to adopt
+    GS_BYTES_UPLOADED,
+    GS_COUNT
+};
+
+// The pair's normalization scale exactly as k_pair_scales forms it (k_setup.hip).
+inline double graph_pair_scale(double scale_pre, double r_src, double r_tgt) {
+    const double rmax = std::fmax(r_src, r_tgt);
+    return scale_pre * (1.0 / rmax);
+}
+
+struct GraphClass {
+    int32_t cloud;          // index into the call's cloud array
+    int32_t k_nrm;          // the largest EstimateNormals k of its uses
+    int32_t n_uses;
+    int32_t nrm_from;       // the class whose kNN / normals this one takes (itself: it runs its own)
+    double norm_center[3];
+    double norm_scale;
+    double f32_center[3];
+};
+
+struct GraphPlan {
+    std::vector<int32_t> use_class;  // [2P]: class of use 2p (source) and 2p + 1 (target)
+    std::vector<GraphClass> classes; // in order of first use
+};
+
+// Plan the classes of P edges.
+//   normalize: the run_se3_* preprocessing (centre on the own centroid, scale by the pair);
+//              otherwise raw coordinates with the f32 copy centred on the edge's target.
+//   center [3 * n_clouds], radius [n_clouds]: GetCenter and the largest |p - center| of every
+//              cloud an edge uses (radius is read only when normalize).
+//   dedupe:    false gives every use a class of its own (sharing level 1).
+// Without normalization the classes of a cloud differ only in the centre of their f32 copy:
+// the exact kNN and the normals are the same bits, so the cloud's first class with normals
+// computes them (nrm_from) and the others copy.
+inline void graph_plan(int32_t n_pairs, const int32_t* src, const int32_t* tgt, bool normalize, double scale_pre,
+                       const double* center, const double* radius, int k_nrm_src, int k_nrm_tgt, bool dedupe,
+                       GraphPlan* plan) {
+    struct Key {
+        int32_t cloud;
+        uint64_t b[4];
+        bool operator<(const Key& o) const {
+            if (cloud != o.cloud) return cloud < o.cloud;
+            return std::memcmp(b, o.b, sizeof(b)) < 0;
+        }
+    };
+    std::map<Key, int32_t> seen;
+    plan->use_class.assign(2 * (size_t)n_pairs, -1);
+    plan->classes.clear();
+    for (int32_t p = 0; p < n_pairs; ++p) {
+        const double scale = normalize ? graph_pair_scale(scale_pre, radius[src[p]], radius[tgt[p]]) : 1.0;
+        for (int side = 0; side < 2; ++side) {
+            const int32_t c = side == 0 ? src[p] : tgt[p];
+            GraphClass g{};
+            g.cloud = c;
+            g.k_nrm = side == 0 ? k_nrm_src : k_nrm_tgt;
+            g.n_uses = 1;
+            g.norm_scale = scale;
+            for (int a = 0; a < 3; ++a) {
+                g.norm_center[a] = normalize ? center[3 * c + a] : 0.0;
+                g.f32_center[a] = normalize ? 0.0 : center[3 * tgt[p] + a];
+            }
+            Key k{};
+            k.cloud = c;
+            std::memcpy(&k.b[0], &g.norm_scale, 8);
+            std::memcpy(&k.b[1], g.f32_center, 24);
+            int32_t id = -1;
+            if (dedupe) {
+                auto it = seen.find(k);
+                if (it != seen.end()) id = it->second;
+            }
+            if (id < 0) {
+                id = (int32_t)plan->classes.size();
+                plan->classes.push_back(g);
+                if (dedupe) seen[k] = id;
+            } else {
+                GraphClass& h = plan->classes[id];
+                h.k_nrm = h.k_nrm > g.k_nrm ? h.k_nrm : g.k_nrm;
+                h.n_uses++;
+            }
+            plan->use_class[2 * (size_t)p + side] = id;
+        }
+    }
+    std::map<int32_t, int32_t> owner;  // cloud -> its first class with normals
+    for (int32_t k = 0; k < (int32_t)plan->classes.size(); ++k) {
+        GraphClass& g = plan->classes[k];
+        g.nrm_from = k;
+        if (normalize || !dedupe || g.k_nrm <= 0) continue;
+        auto it = owner.find(g.cloud);
+        if (it == owner.end()) owner[g.cloud] = k;
+        else if (plan->classes[it->second].k_nrm == g.k_nrm) g.nrm_from = it->second;
+    }
+}
+
+// Argument checks of the graph entries (before the device is looked up).  n_pts may be null
+// only when off is given (n_pts[c] = off[c+1] - off[c]).  Returns 0 or a se3icp_status.
+inline int graph_check(int32_t n_clouds, const int64_t* n_pts, const int64_t* off, int32_t n_pairs,
+                       const int32_t* src, const int32_t* tgt, int method, int n_methods, int32_t sharing,
+                       const void* results) {
+    if (n_clouds <= 0 || n_pairs <= 0 || (!n_pts && !off) || !src || !tgt || !results) return -1;  // INVALID_ARG
+    if (sharing < kGraphSharingMin || sharing > kGraphSharingMax) return -1;
+    if (method < 0 || method >= n_methods) return -2;  // INVALID_METHOD
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (src[p] < 0 || src[p] >= n_clouds || tgt[p] < 0 || tgt[p] >= n_clouds) return -1;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            const int32_t c = side == 0 ? src[p] : tgt[p];
+            const int64_t n = n_pts ? n_pts[c] : off[c + 1] - off[c];
+            if (n <= 0) return -3;  // EMPTY_CLOUD
+        }
+    return 0;
+}
+
+// ---- k_graph.hip
+struct View;
+struct ChunkWork;
+// Per destination cloud.  k_graph_normalize: src_off is the cloud's first slot among the raw
+// columns.  k_graph_share: src_off / src_cloud are the first slot and the cloud whose SE(3)
+// rows it takes (frames != 0), nrm_off the first slot of its normals (its own: none copied).
+struct GraphSeg { int32_t src_off; int32_t src_cloud; int32_t nrm_off; int32_t frames; };
+// a use's normalized columns from the shared raw columns: the arithmetic of k_normalize
+void launch_graph_normalize(const View& v, const ChunkWork* chunks, int nchunks, const GraphSeg* seg,
+                            const double* raw_xyz64, const double* raw_conf64, hipStream_t s);
+// the SE(3) rows and normals of the uses that did not compute their own, from their class's
+void launch_graph_share(const View& v, const ChunkWork* chunks, int nchunks, const GraphSeg* seg, hipStream_t s);
+
+}  // namespace se3icp

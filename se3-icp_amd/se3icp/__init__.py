@@ -14,7 +14,9 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            register_batch, register_batch_device, register_batch_traced, toldi_frames,
                            alpha_grid, register_sweep, register_sweep_device, register_sweep_traced, sweep_params,
                            PairReport, register_batch_report, register_batch_report_device, register_sweep_report,
-                           register_sweep_report_device)
+                           register_sweep_report_device,
+                           expand_edges, last_graph_stats, register_graph, register_graph_device,
+                           register_graph_report, register_graph_traced, register_sequence, sequence_edges)
 from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
@@ -24,4 +26,6 @@ __all__ = [
     "register_sweep", "register_sweep_device", "register_sweep_traced", "alpha_grid", "sweep_params",
     "PairReport", "Report", "ReportOptions", "register_batch_report", "register_batch_report_device",
     "register_sweep_report", "register_sweep_report_device",
+    "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
+    "register_graph_report", "register_graph_traced", "last_graph_stats",
 ]

@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "se3icp_get_result",
     "se3icp_register_batch", "se3icp_register_batch_device", "se3icp_register",
     "se3icp_register_sweep", "se3icp_register_sweep_device",
+    "se3icp_register_graph", "se3icp_register_graph_device", "se3icp_register_graph_report",
+    "se3icp_register_graph_report_device", "se3icp_last_graph_stats",
     "se3icp_report_version", "se3icp_register_batch_report", "se3icp_register_batch_report_device",
     "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
     "se3icp_request_report", "se3icp_get_report",
@@ -129,6 +131,11 @@ class Trace(C.Structure):
     ]
 
 
+# se3icp_last_graph_stats
+GRAPH_STATS = ["clouds", "uses", "classes", "classes_full", "adopted", "rejected_order", "rejected_gap", "no_list",
+               "bytes_uploaded"]
+
+
 class Se3IcpError(RuntimeError):
     def __init__(self, code: int, what: str = ""):
         self.code = code
@@ -185,6 +192,13 @@ def load():
     L.se3icp_register_batch_report_device.argtypes = L.se3icp_register_batch_device.argtypes + [rop, rep]
     L.se3icp_register_sweep_report.argtypes = L.se3icp_register_sweep.argtypes + [rop, rep]
     L.se3icp_register_sweep_report_device.argtypes = L.se3icp_register_sweep_device.argtypes + [rop, rep]
+    L.se3icp_register_graph.argtypes = [C.c_int, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32, ip, ip,
+                                        C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(Result)]
+    L.se3icp_register_graph_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), C.c_int32, ip, ip,
+                                               C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(Result), vp]
+    L.se3icp_register_graph_report.argtypes = L.se3icp_register_graph.argtypes + [rop, rep]
+    L.se3icp_register_graph_report_device.argtypes = L.se3icp_register_graph_device.argtypes + [rop, rep]
+    L.se3icp_last_graph_stats.argtypes = [C.c_int, C.POINTER(C.c_int64), C.c_int]
     L.se3icp_request_report.argtypes = [vp, rop]
     L.se3icp_get_report.argtypes = [vp, rep]
     L.se3icp_register.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(Params),

@@ -651,6 +651,124 @@ def register_sweep_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, m
 
 
 # ---- stage entry points (one per reference function on the hot path)
+# ---- cloud graphs (pairs over a shared set of clouds, each cloud set up once)
+def sequence_edges(n: int) -> list[tuple[int, int]]:
+    """The edges of the reference's odometry drivers over n scans: scan i+1 registered onto
+    scan i (examples/benchmark_kitti.cpp:120-131), as (source, target) cloud indices."""
+    return [(i + 1, i) for i in range(max(0, int(n) - 1))]
+
+
+def expand_edges(clouds, edges):
+    """The (source, target) pair list register_batch takes for `edges` over `clouds`."""
+    return [(clouds[int(s)], clouds[int(t)]) for s, t in edges]
+
+
+def _edge_arrays(edges):
+    n = len(edges)
+    es = (C.c_int32 * max(n, 1))(*[int(s) for s, _ in edges])
+    et = (C.c_int32 * max(n, 1))(*[int(t) for _, t in edges])
+    return n, es, et
+
+
+def register_graph(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
+                   sharing: int = 0) -> list[PairResult]:
+    """Register clouds[s] onto clouds[t] for every (s, t) of `edges`: result p is bitwise
+    register_batch's for that pair, but every distinct cloud is uploaded and ingested once and
+    set up once per normalization it takes part in (se3icp_register_graph).  sharing: 0 the
+    engine's choice, 1 .. 3 see include/se3icp.h."""
+    L = _lib.load()
+    cl = [_as_xyz(c) for c in clouds]
+    nc = len(cl)
+    dp = C.POINTER(C.c_double)
+    cp = (dp * max(nc, 1))(*[a.ctypes.data_as(dp) for a in cl])
+    cn = (C.c_int64 * max(nc, 1))(*[a.shape[0] for a in cl])
+    n, es, et = _edge_arrays(edges)
+    res = (_lib.Result * max(n, 1))()
+    rc = L.se3icp_register_graph(device, nc, cp, cn, n, es, et, _lib.method_id(method),
+                                 C.byref(params or _lib.default_params()), int(sharing), res)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_graph")
+    return _results(res, n)
+
+
+def register_sequence(clouds, method: str, params: _lib.Params | None = None, device: int = 0,
+                      sharing: int = 0) -> list[PairResult]:
+    """register_graph over sequence_edges(len(clouds)): scan i+1 onto scan i."""
+    return register_graph(clouds, sequence_edges(len(clouds)), method, params, device, sharing)
+
+
+def register_graph_device(xyz_ptr: int, off, edges, method: str, params: _lib.Params | None = None,
+                          device: int = 0, stream: int = 0, sharing: int = 0) -> list[PairResult]:
+    """register_graph for clouds already in HBM: xyz_ptr is the device address of the
+    concatenated AoS float64 xyz of every cloud, off the n_clouds+1 point offsets."""
+    L = _lib.load()
+    nc = len(off) - 1
+    co = (C.c_int64 * (nc + 1))(*[int(x) for x in off])
+    n, es, et = _edge_arrays(edges)
+    res = (_lib.Result * max(n, 1))()
+    rc = L.se3icp_register_graph_device(device, nc, C.c_void_p(xyz_ptr), co, n, es, et, _lib.method_id(method),
+                                        C.byref(params or _lib.default_params()), int(sharing), res,
+                                        C.c_void_p(stream) if stream else None)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_graph_device")
+    return _results(res, n)
+
+
+def register_graph_report(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
+                          sharing: int = 0, max_correspondence_distance: float = 0.0, per_point: bool = False):
+    """register_graph plus a PairReport per edge, as register_batch_report: (results, reports)."""
+    L = _lib.load()
+    cl = [_as_xyz(c) for c in clouds]
+    nc = len(cl)
+    dp = C.POINTER(C.c_double)
+    cp = (dp * max(nc, 1))(*[a.ctypes.data_as(dp) for a in cl])
+    cn = (C.c_int64 * max(nc, 1))(*[a.shape[0] for a in cl])
+    n, es, et = _edge_arrays(edges)
+    counts = [cl[int(s)].shape[0] for s, _ in edges]
+    res = (_lib.Result * max(n, 1))()
+    rep = (_lib.Report * max(n, 1))()
+    idx = np.full(sum(counts), -1, np.int32) if per_point else None
+    dist = np.zeros(sum(counts)) if per_point else None
+    opts = _report_options(max_correspondence_distance, idx.ctypes.data if per_point else None,
+                           dist.ctypes.data if per_point else None)
+    rc = L.se3icp_register_graph_report(device, nc, cp, cn, n, es, et, _lib.method_id(method),
+                                        C.byref(params or _lib.default_params()), int(sharing), res, C.byref(opts), rep)
+    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
+        raise _lib.Se3IcpError(rc, "register_graph_report")
+    ii = _split(idx, counts) if per_point else [None] * n
+    dd = _split(dist, counts) if per_point else [None] * n
+    return _results(res, n), [_report(rep[i], ii[i], dd[i]) for i in range(n)]
+
+
+def register_graph_traced(clouds, edges, method: str, params: _lib.Params | None = None, edge: int = 0,
+                          max_iters: int = 160, device: int = 0, sharing: int = 0):
+    """register_graph with the per-iteration record of one edge (see register_batch_traced)."""
+    L = _lib.load()
+    ns = _as_xyz(clouds[int(edges[edge][0])]).shape[0]
+    tr = {"corr_idx": np.full((max_iters, ns), -1, np.int32), "corr_dist": np.zeros((max_iters, ns), np.float32),
+          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
+          "phase": np.zeros(max_iters, np.int32)}
+    t = _lib.Trace(edge, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
+                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
+                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(C.POINTER(C.c_double)),
+                   tr["mse"].ctypes.data_as(C.POINTER(C.c_double)), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)),
+                   0, 0)
+    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
+    try:
+        res = register_graph(clouds, edges, method, params, device, sharing)
+    finally:
+        L.se3icp_set_trace(device, None)
+    n = int(t.iters_recorded)
+    return res, {k: v[:n] for k, v in tr.items()}
+
+
+def last_graph_stats(device: int = 0) -> dict:
+    """Counters of the last register_graph on `device` (se3icp_last_graph_stats)."""
+    out = (C.c_int64 * len(_lib.GRAPH_STATS))()
+    _lib.check(_lib.load().se3icp_last_graph_stats(device, out, len(_lib.GRAPH_STATS)), "last_graph_stats")
+    return {k: int(out[i]) for i, k in enumerate(_lib.GRAPH_STATS)}
+
+
 def toldi_frames(pts, k: int, device: int = 0) -> np.ndarray:
     """computeAllTOLDISE3FramesOMP (ISR.cpp:318-331): (N, 4, 4) frames."""
     pts = _as_xyz(pts)

@@ -112,110 +112,29 @@ int se3icp_device_count(void) {
     return n;
 }
 
-// ------------------------------------------------------------------ batch surface
-int se3icp_register_batch(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
-                          const double* const* tgt_xyz, const int64_t* n_tgt, int method,
-                          const se3icp_params* params, se3icp_result* results) {
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
+// ------------------------------------------------------------------ batch, sweep and report surface
+static se3icp_params params_or_defaults(const se3icp_params* params) {
     se3icp_params p;
     if (params) p = *params; else se3icp_default_params(&p);
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_batch(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, p, results, nullptr);
+    return p;
 }
-
-int se3icp_register_batch_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
-                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method,
-                                 const se3icp_params* params, se3icp_result* results, void* hip_stream) {
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
-    std::vector<const double*> s(n_pairs), t(n_pairs);
-    std::vector<int64_t> ns(n_pairs), nt(n_pairs);
-    for (int i = 0; i < n_pairs; ++i) {
-        s[i] = d_src_xyz + 3 * src_off[i];
-        t[i] = d_tgt_xyz + 3 * tgt_off[i];
-        ns[i] = src_off[i + 1] - src_off[i];
-        nt[i] = tgt_off[i + 1] - tgt_off[i];
-    }
-    se3icp_params p;
-    if (params) p = *params; else se3icp_default_params(&p);
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_batch(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, p, results,
-                             (hipStream_t)hip_stream);
-}
-
-// ------------------------------------------------------------------ parameter sweeps
-// The arguments of a sweep are checked before the device is looked up: a bad call is
-// reported as such on a host without a GPU too.
-static int sweep_check(int32_t n_pairs, const int64_t* n_src, const int64_t* n_tgt, int method, int32_t n_variants,
-                       const se3icp_params* variants, int32_t max_group, const se3icp_result* results) {
-    if (n_pairs <= 0 || !n_src || !n_tgt || !results) return SE3ICP_ERR_INVALID_ARG;
-    if (n_variants <= 0 || !variants || max_group < 0) return SE3ICP_ERR_INVALID_ARG;
-    if (method < 0 || method >= SE3ICP_NUM_METHODS) return SE3ICP_ERR_INVALID_METHOD;
-    for (int32_t p = 0; p < n_pairs; ++p)
-        if (n_src[p] <= 0 || n_tgt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
-    // what shapes the shared setup is common to all variants
-    for (int32_t v = 1; v < n_variants; ++v)
-        if (variants[v].number_of_nn_for_LRF != variants[0].number_of_nn_for_LRF ||
-            variants[v].scale_preprocessing != variants[0].scale_preprocessing)
-            return SE3ICP_ERR_INVALID_ARG;
-    if (method >= SE3ICP_SE3_PT2PT && variants[0].number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
-    return SE3ICP_OK;
-}
-
-int se3icp_register_sweep(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
-                          const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
-                          const se3icp_params* variants, int32_t max_group, se3icp_result* results) {
-    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
-    const int rc = sweep_check(n_pairs, n_src, n_tgt, method, n_variants, variants, max_group, results);
-    if (rc) return rc;
-    for (int32_t p = 0; p < n_pairs; ++p)
-        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_sweep(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants, max_group,
-                             results, nullptr);
-}
-
-int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
-                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method, int32_t n_variants,
-                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
-                                 void* hip_stream) {
-    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
-    std::vector<const double*> s(n_pairs), t(n_pairs);
-    std::vector<int64_t> ns(n_pairs), nt(n_pairs);
-    for (int i = 0; i < n_pairs; ++i) {
-        s[i] = d_src_xyz + 3 * src_off[i];
-        t[i] = d_tgt_xyz + 3 * tgt_off[i];
-        ns[i] = src_off[i + 1] - src_off[i];
-        nt[i] = tgt_off[i + 1] - tgt_off[i];
-    }
-    const int rc = sweep_check(n_pairs, ns.data(), nt.data(), method, n_variants, variants, max_group, results);
-    if (rc) return rc;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_sweep(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, n_variants, variants,
-                             max_group, results, (hipStream_t)hip_stream);
-}
-
-// ------------------------------------------------------------------ registration reports
-// Checked before the device is looked up, as the sweeps' arguments are.
-int se3icp_report_version(void) { return 1; }
 
 // the per-pair pointers and sizes of clouds concatenated in HBM (the *_device entries)
-static void pair_ranges(int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off, const double* d_tgt_xyz,
-                        const int64_t* tgt_off, std::vector<const double*>& s, std::vector<const double*>& t,
-                        std::vector<int64_t>& ns, std::vector<int64_t>& nt) {
-    s.resize(n_pairs); t.resize(n_pairs); ns.resize(n_pairs); nt.resize(n_pairs);
+struct PairRanges {
+    std::vector<const double*> s, t;
+    std::vector<int64_t> ns, nt;
+};
+static int pair_ranges(int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off, const double* d_tgt_xyz,
+                       const int64_t* tgt_off, PairRanges* r) {
+    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
+    r->s.resize(n_pairs); r->t.resize(n_pairs); r->ns.resize(n_pairs); r->nt.resize(n_pairs);
     for (int i = 0; i < n_pairs; ++i) {
-        s[i] = d_src_xyz + 3 * src_off[i];
-        t[i] = d_tgt_xyz + 3 * tgt_off[i];
-        ns[i] = src_off[i + 1] - src_off[i];
-        nt[i] = tgt_off[i + 1] - tgt_off[i];
+        r->s[i] = d_src_xyz + 3 * src_off[i];
+        r->t[i] = d_tgt_xyz + 3 * tgt_off[i];
+        r->ns[i] = src_off[i + 1] - src_off[i];
+        r->nt[i] = tgt_off[i + 1] - tgt_off[i];
     }
+    return SE3ICP_OK;
 }
 
 static int report_check(const se3icp_report_options* opts, const se3icp_report* reports, bool per_point_allowed) {
@@ -225,72 +144,127 @@ static int report_check(const se3icp_report_options* opts, const se3icp_report* 
     return SE3ICP_OK;
 }
 
-static int batch_check(int32_t n_pairs, const int64_t* n_src, const int64_t* n_tgt, int method,
-                       const se3icp_params* params, const se3icp_result* results) {
+// The pairs and the method of a batch or a sweep, and the frames' neighbourhood of `prm` (the
+// batch's parameters, null for the defaults, or the sweep's first variant).
+static int pairs_check(int32_t n_pairs, const double* const* src, const int64_t* n_src, const double* const* tgt,
+                       const int64_t* n_tgt, int method, const se3icp_params* prm, const se3icp_result* results) {
     if (n_pairs <= 0 || !n_src || !n_tgt || !results) return SE3ICP_ERR_INVALID_ARG;
     if (method < 0 || method >= SE3ICP_NUM_METHODS) return SE3ICP_ERR_INVALID_METHOD;
     for (int32_t p = 0; p < n_pairs; ++p)
         if (n_src[p] <= 0 || n_tgt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
-    if (method >= SE3ICP_SE3_PT2PT && params && params->number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
+    if (method >= SE3ICP_SE3_PT2PT && prm && prm->number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        if (!src[p] || !tgt[p]) return SE3ICP_ERR_INVALID_ARG;
     return SE3ICP_OK;
+}
+
+// The four batch entries.  args: the status of the entry's own pointer checks.  The two entries
+// without a report look the device up first and leave every other check to the engine; the
+// report entries check their arguments first, so a bad call is reported as such on a host
+// without a GPU too.
+static int batch_run(int device, int args, int32_t n_pairs, const double* const* src, const int64_t* n_src,
+                     const double* const* tgt, const int64_t* n_tgt, bool on_device, int method,
+                     const se3icp_params* params, se3icp_result* results, void* hip_stream,
+                     const se3icp_report_options* opts, se3icp_report* reports, bool with_report) {
+    if (with_report) {
+        int rc = args ? args : report_check(opts, reports, true);
+        if (!rc) rc = pairs_check(n_pairs, src, n_src, tgt, n_tgt, method, params, results);
+        if (rc) return rc;
+    }
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    if (args) return args;
+    const se3icp_params p = params_or_defaults(params);
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_batch(n_pairs, src, n_src, tgt, n_tgt, on_device, method, p, results, (hipStream_t)hip_stream,
+                             with_report ? opts : nullptr, with_report ? reports : nullptr);
+}
+
+// The four sweep entries: all check their arguments before the device is looked up.
+static int sweep_run(int device, int args, int32_t n_pairs, const double* const* src, const int64_t* n_src,
+                     const double* const* tgt, const int64_t* n_tgt, bool on_device, int method, int32_t n_variants,
+                     const se3icp_params* variants, int32_t max_group, se3icp_result* results, void* hip_stream,
+                     const se3icp_report_options* opts, se3icp_report* reports, bool with_report) {
+    int rc = args;
+    if (!rc && with_report) rc = report_check(opts, reports, false);
+    if (!rc && (n_variants <= 0 || !variants || max_group < 0)) rc = SE3ICP_ERR_INVALID_ARG;
+    if (!rc) rc = pairs_check(n_pairs, src, n_src, tgt, n_tgt, method, variants, results);
+    // what shapes the shared setup is common to all variants
+    for (int32_t v = 1; !rc && v < n_variants; ++v)
+        if (variants[v].number_of_nn_for_LRF != variants[0].number_of_nn_for_LRF ||
+            variants[v].scale_preprocessing != variants[0].scale_preprocessing)
+            rc = SE3ICP_ERR_INVALID_ARG;
+    if (rc) return rc;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->register_sweep(n_pairs, src, n_src, tgt, n_tgt, on_device, method, n_variants, variants, max_group,
+                             results, (hipStream_t)hip_stream, with_report ? opts : nullptr,
+                             with_report ? reports : nullptr);
+}
+
+int se3icp_register_batch(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                          const double* const* tgt_xyz, const int64_t* n_tgt, int method,
+                          const se3icp_params* params, se3icp_result* results) {
+    return batch_run(device, SE3ICP_OK, n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, params, results,
+                     nullptr, nullptr, nullptr, false);
+}
+
+int se3icp_register_batch_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method,
+                                 const se3icp_params* params, se3icp_result* results, void* hip_stream) {
+    PairRanges r;
+    const int args = pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, &r);
+    return batch_run(device, args, n_pairs, r.s.data(), r.ns.data(), r.t.data(), r.nt.data(), true, method, params,
+                     results, hip_stream, nullptr, nullptr, false);
 }
 
 int se3icp_register_batch_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
                                  const double* const* tgt_xyz, const int64_t* n_tgt, int method,
                                  const se3icp_params* params, se3icp_result* results,
                                  const se3icp_report_options* opts, se3icp_report* reports) {
-    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
-    int rc = report_check(opts, reports, true);
-    if (rc) return rc;
-    rc = batch_check(n_pairs, n_src, n_tgt, method, params, results);
-    if (rc) return rc;
-    for (int32_t p = 0; p < n_pairs; ++p)
-        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_params p;
-    if (params) p = *params; else se3icp_default_params(&p);
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_batch(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, p, results, nullptr, opts, reports);
+    const int args = (!src_xyz || !tgt_xyz) ? SE3ICP_ERR_INVALID_ARG : SE3ICP_OK;
+    return batch_run(device, args, n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, params, results, nullptr,
+                     opts, reports, true);
 }
 
 int se3icp_register_batch_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
                                         const double* d_tgt_xyz, const int64_t* tgt_off, int method,
                                         const se3icp_params* params, se3icp_result* results, void* hip_stream,
                                         const se3icp_report_options* opts, se3icp_report* reports) {
-    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
-    int rc = report_check(opts, reports, true);
-    if (rc) return rc;
-    std::vector<const double*> s, t;
-    std::vector<int64_t> ns, nt;
-    pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, s, t, ns, nt);
-    rc = batch_check(n_pairs, ns.data(), nt.data(), method, params, results);
-    if (rc) return rc;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_params p;
-    if (params) p = *params; else se3icp_default_params(&p);
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_batch(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, p, results,
-                             (hipStream_t)hip_stream, opts, reports);
+    PairRanges r;
+    const int args = pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, &r);
+    return batch_run(device, args, n_pairs, r.s.data(), r.ns.data(), r.t.data(), r.nt.data(), true, method, params,
+                     results, hip_stream, opts, reports, true);
 }
+
+int se3icp_register_sweep(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
+                          const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
+                          const se3icp_params* variants, int32_t max_group, se3icp_result* results) {
+    const int args = (!src_xyz || !tgt_xyz) ? SE3ICP_ERR_INVALID_ARG : SE3ICP_OK;
+    return sweep_run(device, args, n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants,
+                     max_group, results, nullptr, nullptr, nullptr, false);
+}
+
+int se3icp_register_sweep_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
+                                 const double* d_tgt_xyz, const int64_t* tgt_off, int method, int32_t n_variants,
+                                 const se3icp_params* variants, int32_t max_group, se3icp_result* results,
+                                 void* hip_stream) {
+    PairRanges r;
+    const int args = pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, &r);
+    return sweep_run(device, args, n_pairs, r.s.data(), r.ns.data(), r.t.data(), r.nt.data(), true, method, n_variants,
+                     variants, max_group, results, hip_stream, nullptr, nullptr, false);
+}
+
+int se3icp_report_version(void) { return 1; }
 
 int se3icp_register_sweep_report(int device, int32_t n_pairs, const double* const* src_xyz, const int64_t* n_src,
                                  const double* const* tgt_xyz, const int64_t* n_tgt, int method, int32_t n_variants,
                                  const se3icp_params* variants, int32_t max_group, se3icp_result* results,
                                  const se3icp_report_options* opts, se3icp_report* reports) {
-    if (!src_xyz || !tgt_xyz) return SE3ICP_ERR_INVALID_ARG;
-    int rc = report_check(opts, reports, false);
-    if (rc) return rc;
-    rc = sweep_check(n_pairs, n_src, n_tgt, method, n_variants, variants, max_group, results);
-    if (rc) return rc;
-    for (int32_t p = 0; p < n_pairs; ++p)
-        if (!src_xyz[p] || !tgt_xyz[p]) return SE3ICP_ERR_INVALID_ARG;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_sweep(n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants, max_group,
-                             results, nullptr, opts, reports);
+    const int args = (!src_xyz || !tgt_xyz) ? SE3ICP_ERR_INVALID_ARG : SE3ICP_OK;
+    return sweep_run(device, args, n_pairs, src_xyz, n_src, tgt_xyz, n_tgt, false, method, n_variants, variants,
+                     max_group, results, nullptr, opts, reports, true);
 }
 
 int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const double* d_src_xyz, const int64_t* src_off,
@@ -298,19 +272,10 @@ int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const doubl
                                         int32_t n_variants, const se3icp_params* variants, int32_t max_group,
                                         se3icp_result* results, void* hip_stream,
                                         const se3icp_report_options* opts, se3icp_report* reports) {
-    if (n_pairs <= 0 || !d_src_xyz || !d_tgt_xyz || !src_off || !tgt_off) return SE3ICP_ERR_INVALID_ARG;
-    int rc = report_check(opts, reports, false);
-    if (rc) return rc;
-    std::vector<const double*> s, t;
-    std::vector<int64_t> ns, nt;
-    pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, s, t, ns, nt);
-    rc = sweep_check(n_pairs, ns.data(), nt.data(), method, n_variants, variants, max_group, results);
-    if (rc) return rc;
-    Engine* e = usable_engine(device);
-    if (!e) return SE3ICP_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(e->mutex());
-    return e->register_sweep(n_pairs, s.data(), ns.data(), t.data(), nt.data(), true, method, n_variants, variants,
-                             max_group, results, (hipStream_t)hip_stream, opts, reports);
+    PairRanges r;
+    const int args = pair_ranges(n_pairs, d_src_xyz, src_off, d_tgt_xyz, tgt_off, &r);
+    return sweep_run(device, args, n_pairs, r.s.data(), r.ns.data(), r.t.data(), r.nt.data(), true, method, n_variants,
+                     variants, max_group, results, hip_stream, opts, reports, true);
 }
 
 // ------------------------------------------------------------------ cloud graphs
@@ -331,8 +296,7 @@ static int graph_run(int device, int32_t n_clouds, const double* const* xyz, con
         if (!xyz[src_cloud[p]] || !xyz[tgt_cloud[p]]) return SE3ICP_ERR_INVALID_ARG;
     Engine* e = usable_engine(device);
     if (!e) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_params p;
-    if (params) p = *params; else se3icp_default_params(&p);
+    const se3icp_params p = params_or_defaults(params);
     std::lock_guard<std::mutex> lk(e->mutex());
     return e->register_graph(n_clouds, xyz, n_pts, n_pairs, src_cloud, tgt_cloud, on_device, method, p, sharing, results,
                              (hipStream_t)hip_stream, with_report ? opts : nullptr, with_report ? reports : nullptr);

@@ -57,17 +57,68 @@ bool decode_method(int method, MethodInfo* mi) {
     }
 }
 
-template <class T>
-int pinned(T*& p, size_t& cap, size_t count) {
-    if (cap >= count && p) return 0;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    size_t want = std::max<size_t>(count, 16);
-    if (hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault) != hipSuccess) {
-        cap = 0;
-        return SE3ICP_ERR_OUT_OF_MEMORY;
+// The plan of `method` with number_of_nn_for_LRF = k_lrf; SE3ICP_ERR_INVALID_METHOD, or
+// SE3ICP_ERR_INVALID_ARG for an SE(3) method without neighbours for its frames.
+int plan_method(int method, int k_lrf, MethodPlan* mp) {
+    MethodInfo mi;
+    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
+    *mp = MethodPlan{mi.kind, mi.est, mi.kind != KIND_ICP, 0, 0, 0, 1};
+    mp->k_lrf = mp->se3 ? k_lrf : 0;
+    if (mp->se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
+    if (mi.est == EST_PT2PL) mp->k_nrm_t = 30;                    // target_.EstimateNormals() default KNN(30)
+    if (mi.est == EST_GICP) mp->k_nrm_s = mp->k_nrm_t = 20;       // InitializePointCloudForGeneralizedICP KNN(20)
+    mp->kmax = std::max({mp->k_lrf, mp->k_nrm_s, mp->k_nrm_t, 1});
+    return 0;
+}
+
+// The setup table entry of a pair's source (side 0) or target (side 1).  cf_now: a cf target's
+// 12-D search rows are formed by this setup (a sweep forms them per variant instead).
+CloudSetup cloud_setup(const MethodPlan& mp, int side, double alpha, double beta, bool cf_now) {
+    CloudSetup st{};
+    st.k_lrf = mp.k_lrf;
+    st.k_nrm = side == 0 ? mp.k_nrm_s : mp.k_nrm_t;
+    st.k_knn = std::max(st.k_lrf, st.k_nrm);
+    st.want_cov = mp.est == EST_GICP;
+    st.want_conf = mp.kind == KIND_CF;
+    st.is_target = side;
+    st.cf_target = cf_now && mp.kind == KIND_CF && side == 1;
+    st.alpha = alpha;
+    st.beta = beta;
+    st.norm_scale = 1.0;
+    return st;
+}
+
+// The plan of a batch's or a sweep's method and the check of its pairs' clouds, in the order
+// the entries report them: the method, the clouds (SE3ICP_ERR_EMPTY_CLOUD, then
+// SE3ICP_ERR_INVALID_ARG for a null cloud, pair by pair), the frames' k.
+int plan_pairs(int method, int k_lrf, int npairs, const double* const* src, const int64_t* ns,
+               const double* const* tgt, const int64_t* nt, MethodPlan* mp) {
+    const int rc = plan_method(method, k_lrf, mp);
+    if (rc == SE3ICP_ERR_INVALID_METHOD) return rc;
+    for (int p = 0; p < npairs; ++p) {
+        if (ns[p] <= 0 || nt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+        if (!src[p] || !tgt[p]) return SE3ICP_ERR_INVALID_ARG;
     }
-    cap = want;
+    return rc;
+}
+
+// The clouds some edge of a graph uses, in cloud order: slot[c] is cloud c's place in `used`
+// (-1: unused).  SE3ICP_ERR_INVALID_ARG for an edge outside the set or a used cloud that is
+// null, SE3ICP_ERR_EMPTY_CLOUD for an empty one.
+int graph_used_clouds(int C, const double* const* xyz, const int64_t* npts, int P, const int32_t* esrc,
+                      const int32_t* etgt, std::vector<int32_t>* slot, std::vector<int32_t>* used) {
+    slot->assign(C, -1);
+    for (int p = 0; p < P; ++p) {
+        if (esrc[p] < 0 || esrc[p] >= C || etgt[p] < 0 || etgt[p] >= C) return SE3ICP_ERR_INVALID_ARG;
+        (*slot)[esrc[p]] = (*slot)[etgt[p]] = 0;
+    }
+    for (int c = 0; c < C; ++c)
+        if ((*slot)[c] == 0) {
+            if (npts[c] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+            if (!xyz[c]) return SE3ICP_ERR_INVALID_ARG;
+            (*slot)[c] = (int32_t)used->size();
+            used->push_back(c);
+        }
     return 0;
 }
 
@@ -128,39 +179,17 @@ int Engine::init() {
     return 0;
 }
 
-std::vector<DevBuf*> Engine::all_bufs() {
-    return {&d_clouds_, &d_setup_, &d_pairs_, &d_cloud_of_, &d_inptr_, &d_in_, &d_xyz64_, &d_xyz32_,
-                     &d_fr64_, &d_fr32_, &d_nrm64_, &d_tgeo_, &d_conf64_, &d_knn_,
-                     &d_corr_idx_, &d_corr_dist_, &d_flag_count_, &d_gcost_, &d_cls_, &d_trim_key_, &d_red_partial_,
-                     &d_red_out_, &d_work_, &d_wb_, &d_wn_, &d_chunks_, &d_partial_, &d_centers_,
-                     &d_rechecked_, &d_keys0_, &d_vals1_, &d_sort_tmp_, &d_stats_,
-                     &d_qlist_, &d_qcount_, &d_hist_, &d_cert_, &d_sqlist_, &d_state_, &d_trim_cand_, &d_trim_ctr_, &d_scales_, &d_trim_hist_,
-                     &d_lrf_fb_, &d_lrf_fbn_, &d_big_d_, &d_big_i_, &d_raw_, &d_sweep_w_,
-                     &d_rep_partial_, &d_rep_out_, &d_rep_off_, &d_rep_idx_, &d_rep_dist_,
-                     &t3_.perm, &t3_.pos, &t3_.vec, &t3_.vec64, &t3_.vec64a, &t3_.blo, &t3_.bhi, &t3_.lo, &t3_.hi, &t3_.scr,
-                     &t12_.perm, &t12_.pos, &t12_.vec, &t12_.vec64, &t12_.blo, &t12_.bhi, &t12_.lo, &t12_.hi, &t12_.scr,
-                     &t12_.vecT,
-                     &g_raw_xyz_, &g_raw_conf_, &g_seg_, &g_chunks_};
-}
-
 Engine::~Engine() {
     if (!ok_) return;
     (void)hipSetDevice(dev_);
-    for (DevBuf* b : all_bufs())
+    for (DevBuf* b : bufs_)
         if (b->p) (void)hipFree(b->p);
-    if (h_pairs_) (void)hipHostFree(h_pairs_);
-    if (h_red_) (void)hipHostFree(h_red_);
-    if (h_partial_) (void)hipHostFree(h_partial_);
-    if (h_rechecked_) (void)hipHostFree(h_rechecked_);
-    if (h_hist_) (void)hipHostFree(h_hist_);
-    if (h_rep_) (void)hipHostFree(h_rep_);
-    if (h_lrf_stats_) (void)hipHostFree(h_lrf_stats_);
-    if (h_loop_stats_) (void)hipHostFree(h_loop_stats_);
+    for (PinnedMem* m : pins_)
+        if (m->mem) (void)hipHostFree(m->mem);
     for (auto& e : ev_)
         if (e) (void)hipEventDestroy(e);
     for (auto& e : loop_ev_)
         if (e) (void)hipEventDestroy(e);
-    if (h_state_) (void)hipHostFree(h_state_);
     if (h_phase_) (void)hipHostFree(h_phase_);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -311,9 +340,7 @@ int Engine::build_tree(int D, const float* vec, hipStream_t s, const double* vec
 }
 
 // ----------------------------------------------------------------------------- setup
-int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool normalize_pairs, double scale_pre,
-                         bool build12, std::vector<double>* centers_out, std::vector<double>* scales_out,
-                         hipStream_t s) {
+int Engine::upload_clouds(const std::vector<CloudReq>& clouds, bool on_device, hipStream_t s) {
     nclouds_ = (int)clouds.size();
     h_clouds_.assign(nclouds_, CloudDev{});
     h_setup_.resize(nclouds_);
@@ -346,17 +373,40 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
         !ensure<ChunkWork>(d_chunks_, nch) || !ensure<const double*>(d_inptr_, nclouds_) ||
         !ensure<double>(d_partial_, (size_t)nch * 9) || !ensure<double>(d_centers_, 3 * (size_t)nclouds_))
         return SE3ICP_ERR_OUT_OF_MEMORY;
-    if (pinned(h_partial_, h_partial_cap_, (size_t)nch * 9 + 8)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    if (h_partial_.reserve((size_t)nch * 9 + 8)) return SE3ICP_ERR_OUT_OF_MEMORY;
     HIPCHK(hipMemcpyAsync(d_clouds_.p, h_clouds_.data(), sizeof(CloudDev) * nclouds_, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * nclouds_, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_chunks_.p, h_chunks_.data(), sizeof(ChunkWork) * nch, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_inptr_.p, h_inptr_.data(), sizeof(double*) * nclouds_, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+// (the summation order is part of the result: it is the centroid every f32 copy is taken around)
+int Engine::host_centroids(hipStream_t s, std::vector<double>* cen) {
+    const int nch = (int)h_chunks_.size();
+    HIPCHK(hipMemcpyAsync(h_partial_, d_partial_.p, sizeof(double) * 9 * nch, hipMemcpyDeviceToHost, s));
+    SYNC_STREAM(s);
+    std::vector<double> sum(3 * (size_t)nclouds_, 0.0);
+    for (int k = 0; k < nch; ++k)
+        for (int a = 0; a < 3; ++a) sum[3 * (size_t)h_chunks_[k].cloud + a] += h_partial_[9 * (size_t)k + a];
+    cen->assign(3 * (size_t)nclouds_, 0.0);
+    for (int c = 0; c < nclouds_; ++c)
+        for (int a = 0; a < 3; ++a)
+            (*cen)[3 * (size_t)c + a] = h_clouds_[c].n > 0 ? sum[3 * (size_t)c + a] / (double)h_clouds_[c].n : 0.0;
+    return 0;
+}
+
+int Engine::setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bool pairs, bool normalize,
+                         double scale_pre, hipStream_t s) {
+    int rc = upload_clouds(clouds, on_device, s);
+    if (rc) return rc;
+    const int nch = (int)h_chunks_.size();
     View v = view();
 
     // 1) ingest: SoA copy + sums + bbox
     launch_ingest(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
     HIPCHK(hipGetLastError());
-    if (normalize_pairs) {
+    if (normalize) {
         // 2) normalization parameters (ISR.cpp:568-574) on the device: no host round trip;
         // the centers (d_centers_) and scales (d_scales_) stay there for the loop and the
         // final de-normalization
@@ -370,23 +420,12 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
         for (int c = 0; c < nclouds_; ++c)  // (the device holds the normalization fields)
             for (int a = 0; a < 3; ++a) h_setup_[c].f32_center[a] = 0.0;
     } else {
-        HIPCHK(hipMemcpyAsync(h_partial_, d_partial_.p, sizeof(double) * 9 * nch, hipMemcpyDeviceToHost, s));
-        SYNC_STREAM(s);
-        std::vector<double> cen(3 * nclouds_, 0.0);
-        {
-            std::vector<double> sum(3 * nclouds_, 0.0);
-            for (int k = 0; k < nch; ++k) {
-                const int c = h_chunks_[k].cloud;
-                for (int a = 0; a < 3; ++a) sum[3 * c + a] += h_partial_[9 * k + a];
-            }
-            for (int c = 0; c < nclouds_; ++c)
-                for (int a = 0; a < 3; ++a)
-                    cen[3 * c + a] = clouds[c].n > 0 ? sum[3 * c + a] / (double)clouds[c].n : 0.0;
-        }
-        if (centers_out) *centers_out = cen;
+        std::vector<double> cen;
+        rc = host_centroids(s, &cen);
+        if (rc) return rc;
         for (int c = 0; c < nclouds_; ++c) {
             // raw coordinates; f32 copies centered on the target (pairs) / own centroid (single clouds)
-            const int cc = (nclouds_ % 2 == 0 && npairs_ > 0) ? (c | 1) : c;
+            const int cc = pairs ? (c | 1) : c;
             for (int a = 0; a < 3; ++a) {
                 h_setup_[c].norm_center[a] = 0.0;
                 h_setup_[c].f32_center[a] = cen[3 * cc + a];
@@ -401,17 +440,11 @@ int Engine::setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool nor
     HIPCHK(hipGetLastError());
 
     // 4) 3-D kd-trees of every cloud (kNN for TOLDI / normals, and the R3 NN of the loop)
-    int rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+    rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
     if (rc) return rc;
     rc = setup_knn(s);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    // 5) 12-D kd-trees over the alpha/beta-weighted SE(3) elements
-    have12_ = build12;
-    if (build12) {
-        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);  // f64 source elements in tree order
-        if (rc) return rc;
-    }
     return 0;
 }
 
@@ -474,7 +507,7 @@ int Engine::setup_knn(hipStream_t s) {
         HIPCHK(hipEventRecord(ev_[7], s));
         HIPCHK(hipGetLastError());
         // work counters: copied now, read at the next synchronisation (read_lrf_stats)
-        if (pinned(h_lrf_stats_, h_lrf_stats_cap_, (size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
+        if (h_lrf_stats_.reserve((size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
         HIPCHK(hipMemcpyAsync(h_lrf_stats_, d_stats_.p, sizeof(unsigned long long) * kStatCols * kStatSlots,
                               hipMemcpyDeviceToHost, s));
         lrf_stats_pending_ = true;
@@ -532,7 +565,7 @@ int Engine::setup_chunks(int npairs, hipStream_t s) {
         !ensure<double>(d_hist_, (size_t)kHist * npairs * 12) || !ensure<uint32_t>(d_gcost_, (size_t)nchunks_ * 16) ||
         !ensure<int32_t>(d_cls_, nn_cls_words(nchunks_)))
         return SE3ICP_ERR_OUT_OF_MEMORY;
-    if (pinned(h_hist_, h_hist_cap_, (size_t)npairs * 12)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    if (h_hist_.reserve((size_t)npairs * 12)) return SE3ICP_ERR_OUT_OF_MEMORY;
     HIPCHK(hipMemsetAsync(d_cert_.p, 0xff, sizeof(NNCert) * ld_, s));  // iteration -1: no certificate
     HIPCHK(hipMemsetAsync(d_gcost_.p, 0, sizeof(uint32_t) * nchunks_ * 16, s));
     HIPCHK(hipMemsetAsync(d_cls_.p, 0, sizeof(int32_t) * 2 * 8 * 16, s));
@@ -540,67 +573,34 @@ int Engine::setup_chunks(int npairs, hipStream_t s) {
 }
 
 // ----------------------------------------------------------------------------- batch registration
-int Engine::register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
-                           const int64_t* nt, bool on_device, int method, const se3icp_params& prm,
-                           se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
-                           se3icp_report* reports) {
+// The opening of a registration call (see engine.hpp).
+int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_trace* tr = trace_;  // one-shot: the record covers this batch only
+    se3icp_trace* tr = c->tr = trace_;  // one-shot: the record covers this call only
     trace_ = nullptr;
-    if (npairs <= 0 || !src || !tgt || !ns || !nt || !out) return SE3ICP_ERR_INVALID_ARG;
-    if (tr && (tr->pair < 0 || tr->pair >= npairs || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
+    if (args) return args;
+    if (tr && (tr->pair < 0 || (int64_t)tr->pair >= nslots || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
     if (tr) tr->iters_recorded = 0;
-    MethodInfo mi;
-    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
-    for (int p = 0; p < npairs; ++p) {
-        if (ns[p] <= 0 || nt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
-        if (!src[p] || !tgt[p]) return SE3ICP_ERR_INVALID_ARG;
-    }
-    const bool se3 = mi.kind != KIND_ICP;
-    const int k_lrf = se3 ? prm.number_of_nn_for_LRF : 0;
-    if (se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
-    int k_nrm_s = 0, k_nrm_t = 0;
-    if (mi.est == EST_PT2PL) k_nrm_t = 30;                    // target_.EstimateNormals() default KNN(30)
-    if (mi.est == EST_GICP) { k_nrm_s = 20; k_nrm_t = 20; }   // InitializePointCloudForGeneralizedICP KNN(20)
-    const int kmax = std::max({k_lrf, k_nrm_s, k_nrm_t, 1});
+    if (rest) return rest;
     HIPCHK(hipSetDevice(dev_));
-    hipStream_t s = user_stream ? user_stream : stream_;
+    c->s = user_stream ? user_stream : stream_;
     ktimes_ = KernelTimes{};
     // phase times on the GPU timeline (the host does not wait for the setup): events
     // 12 (begin), 13 (setup done), 14 (loop done)
-    HIPCHK(hipEventRecord(ev_[12], s));
+    HIPCHK(hipEventRecord(ev_[12], c->s));
+    return 0;
+}
 
-    npairs_ = npairs;
-    int64_t ntot = 0;
-    for (int p = 0; p < npairs; ++p) ntot += ns[p] + nt[p];
-    int rc = alloc_points(ntot, kmax);
+// Everything behind the clouds' setup (see engine.hpp).
+int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const int64_t* nt,
+                      const se3icp_params* vprm, int pairs_per_variant, bool sweep, const Call& c, se3icp_result* out,
+                      const se3icp_report_options* ropts, se3icp_report* reports) {
+    hipStream_t s = c.s;
+    int rc = 0;
+    // 12-D kd-trees over the alpha/beta-weighted SE(3) elements (f64 source elements in tree order)
+    if (mp.se3) rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
     if (rc) return rc;
     rc = prepare_pairs(npairs, ns, nt, s);
-    if (rc) return rc;
-
-    // ---- setup (ISR.cpp:568-648)
-    std::vector<CloudReq> clouds(2 * npairs);
-    for (int p = 0; p < npairs; ++p) {
-        for (int side = 0; side < 2; ++side) {
-            CloudReq& r = clouds[2 * p + side];
-            r.in = side == 0 ? src[p] : tgt[p];
-            r.n = side == 0 ? ns[p] : nt[p];
-            CloudSetup& st = r.st;
-            st = CloudSetup{};
-            st.k_lrf = k_lrf;
-            st.k_nrm = side == 0 ? k_nrm_s : k_nrm_t;
-            st.k_knn = std::max(st.k_lrf, st.k_nrm);
-            st.want_cov = mi.est == EST_GICP;
-            st.want_conf = mi.kind == KIND_CF;
-            st.is_target = side == 1;
-            st.cf_target = (mi.kind == KIND_CF && side == 1);
-            st.alpha = prm.alpha_rot;
-            st.beta = prm.beta_transl;
-            st.norm_scale = 1.0;
-        }
-    }
-    std::vector<double> centers;  // run_icp only (run_se3_*: normalization parameters on the device)
-    rc = setup_clouds(clouds, on_device, se3, prm.scale_preprocessing, se3, &centers, nullptr, s);
     if (rc) return rc;
     rc = setup_chunks(npairs, s);
     if (rc) return rc;
@@ -609,7 +609,35 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
     for (double& t : trace_prev_) t = 0;
     HIPCHK(hipEventRecord(ev_[13], s));
     const ReportReq rq{ropts, reports};
-    return run_loop(npairs, ns, mi.kind, mi.est, &prm, npairs, false, tr, out, s, (ropts && reports) ? &rq : nullptr);
+    return run_loop(npairs, ns, mp.kind, mp.est, vprm, pairs_per_variant, sweep, c.tr, out, s,
+                    (ropts && reports) ? &rq : nullptr);
+}
+
+int Engine::register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
+                           const int64_t* nt, bool on_device, int method, const se3icp_params& prm,
+                           se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
+                           se3icp_report* reports) {
+    const int args = (npairs <= 0 || !src || !tgt || !ns || !nt || !out) ? SE3ICP_ERR_INVALID_ARG : 0;
+    MethodPlan mp{};
+    const int rest = args ? 0 : plan_pairs(method, prm.number_of_nn_for_LRF, npairs, src, ns, tgt, nt, &mp);
+    Call call;
+    int rc = open_call(args, npairs, rest, user_stream, &call);
+    if (rc) return rc;
+
+    npairs_ = npairs;
+    int64_t ntot = 0;
+    for (int p = 0; p < npairs; ++p) ntot += ns[p] + nt[p];
+    rc = alloc_points(ntot, mp.kmax);
+    if (rc) return rc;
+    // ---- setup (ISR.cpp:568-648)
+    std::vector<CloudReq> clouds(2 * npairs);
+    for (int p = 0; p < npairs; ++p)
+        for (int side = 0; side < 2; ++side)
+            clouds[2 * p + side] = CloudReq{side == 0 ? src[p] : tgt[p], side == 0 ? ns[p] : nt[p],
+                                            cloud_setup(mp, side, prm.alpha_rot, prm.beta_transl, true)};
+    rc = setup_clouds(clouds, on_device, true, mp.se3, prm.scale_preprocessing, call.s);
+    if (rc) return rc;
+    return run_pairs(mp, npairs, ns, nt, &prm, npairs, false, call, out, ropts, reports);
 }
 
 // Work table of k_reduce and the per-pair buffers of a batch (see engine.hpp).
@@ -636,8 +664,7 @@ int Engine::prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipS
         !ensure<double>(d_red_partial_, (size_t)nwork_ * kRedVals) || !ensure<double>(d_red_out_, (size_t)npairs * kRedVals) ||
         !ensure<int32_t>(d_rechecked_, npairs))
         return SE3ICP_ERR_OUT_OF_MEMORY;
-    if (pinned(h_pairs_, h_pairs_cap_, npairs) || pinned(h_red_, h_red_cap_, (size_t)npairs * kRedVals) ||
-        pinned(h_rechecked_, h_rechecked_cap_, npairs))
+    if (h_pairs_.reserve(npairs) || h_red_.reserve((size_t)npairs * kRedVals) || h_rechecked_.reserve(npairs))
         return SE3ICP_ERR_OUT_OF_MEMORY;
     HIPCHK(hipMemcpyAsync(d_work_.p, h_work_.data(), sizeof(BlockWork) * nwork_, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_wb_.p, h_wb_.data(), sizeof(int32_t) * npairs, hipMemcpyHostToDevice, s));
@@ -656,7 +683,7 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
 
     // ---- per-pair loop state (ISR.cpp:629-651); iteration 1 is opened here, every later
     // one by k_reduce_final on the device (pairmath.hpp), so the host only queues work
-    if (!ensure<PairState>(d_state_, npairs) || pinned(h_state_, h_state_cap_, npairs))
+    if (!ensure<PairState>(d_state_, npairs) || h_state_.reserve(npairs))
         return SE3ICP_ERR_OUT_OF_MEMORY;
     if (h_phase_cap_ < (size_t)npairs * kLoopRing) {  // coherent host memory the device writes directly
         if (h_phase_) (void)hipHostFree(h_phase_);
@@ -886,7 +913,7 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
     if (se3) HIPCHK(hipMemcpyAsync(h_partial_, d_centers_.p, sizeof(double) * 3 * nbase, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_rechecked_, d_rechecked_.p, sizeof(int32_t) * npairs, hipMemcpyDeviceToHost, s));
     {
-        if (pinned(h_loop_stats_, h_loop_stats_cap_, (size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
+        if (h_loop_stats_.reserve((size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
         const unsigned long long* stats = h_loop_stats_;
         HIPCHK(hipMemcpyAsync(h_loop_stats_, d_stats_.p, sizeof(unsigned long long) * kStatCols * kStatSlots,
                               hipMemcpyDeviceToHost, s));
@@ -992,7 +1019,7 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
 int Engine::queue_report(int npairs, const int64_t* ns, const ReportReq& rq, hipStream_t s) {
     const se3icp_report_options& o = *rq.opts;
     if (!ensure<double>(d_rep_partial_, (size_t)nwork_ * kRepVals) || !ensure<double>(d_rep_out_, (size_t)npairs * kRepVals) ||
-        pinned(h_rep_, h_rep_cap_, (size_t)npairs * kRepVals))
+        h_rep_.reserve((size_t)npairs * kRepVals))
         return SE3ICP_ERR_OUT_OF_MEMORY;
     ReportArgs a{};
     a.state = (const PairState*)d_state_.p;
@@ -1055,36 +1082,21 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
                            const int64_t* nt, bool on_device, int method, int nvariants,
                            const se3icp_params* variants, int max_group, se3icp_result* out, hipStream_t user_stream,
                            const se3icp_report_options* ropts, se3icp_report* reports) {
-    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_trace* tr = trace_;  // one-shot: the record covers this sweep only
-    trace_ = nullptr;
-    if (P <= 0 || !src || !tgt || !ns || !nt || !out || nvariants <= 0 || !variants || max_group < 0)
-        return SE3ICP_ERR_INVALID_ARG;
-    if (tr && (tr->pair < 0 || (int64_t)tr->pair >= (int64_t)nvariants * P || tr->max_iters < 0))
-        return SE3ICP_ERR_INVALID_ARG;
-    if (tr) tr->iters_recorded = 0;
-    MethodInfo mi;
-    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
-    for (int p = 0; p < P; ++p) {
-        if (ns[p] <= 0 || nt[p] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
-        if (!src[p] || !tgt[p]) return SE3ICP_ERR_INVALID_ARG;
-    }
+    const int args = (P <= 0 || !src || !tgt || !ns || !nt || !out || nvariants <= 0 || !variants || max_group < 0)
+                         ? SE3ICP_ERR_INVALID_ARG : 0;
+    MethodPlan mp{};
+    int rest = args ? 0 : plan_pairs(method, variants[0].number_of_nn_for_LRF, P, src, ns, tgt, nt, &mp);
+    for (int k = 1; !args && !rest && k < nvariants; ++k)  // what shapes the shared setup is common to all variants
+        if (variants[k].number_of_nn_for_LRF != variants[0].number_of_nn_for_LRF ||
+            variants[k].scale_preprocessing != variants[0].scale_preprocessing)
+            rest = SE3ICP_ERR_INVALID_ARG;
+    Call call;
+    int rc = open_call(args, (int64_t)nvariants * P, rest, user_stream, &call);
+    if (rc) return rc;
+    se3icp_trace* const tr = call.tr;
+    hipStream_t s = call.s;
+    const bool se3 = mp.se3;
     const se3icp_params& prm0 = variants[0];
-    for (int k = 1; k < nvariants; ++k)
-        if (variants[k].number_of_nn_for_LRF != prm0.number_of_nn_for_LRF ||
-            variants[k].scale_preprocessing != prm0.scale_preprocessing)
-            return SE3ICP_ERR_INVALID_ARG;
-    const bool se3 = mi.kind != KIND_ICP;
-    const int k_lrf = se3 ? prm0.number_of_nn_for_LRF : 0;
-    if (se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
-    int k_nrm_s = 0, k_nrm_t = 0;
-    if (mi.est == EST_PT2PL) k_nrm_t = 30;
-    if (mi.est == EST_GICP) { k_nrm_s = 20; k_nrm_t = 20; }
-    const int kmax = std::max({k_lrf, k_nrm_s, k_nrm_t, 1});
-    HIPCHK(hipSetDevice(dev_));
-    hipStream_t s = user_stream ? user_stream : stream_;
-    ktimes_ = KernelTimes{};
-    HIPCHK(hipEventRecord(ev_[12], s));
 
     int64_t N = 0;
     int max_n = 1;
@@ -1098,14 +1110,14 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     int64_t held = 0;
-    for (DevBuf* b : all_bufs()) held += (int64_t)b->bytes;
+    for (const DevBuf* b : bufs_) held += (int64_t)b->bytes;
     const int G = sweep_group_size(nvariants, max_group, N, nbase, kSweepBytesPerPoint, kSweepBytesPerCloud,
                                    (int64_t)free_b + held);
     const int ngroups = sweep_num_groups(nvariants, G);
 
     // buffers of the largest group, before the shared setup fills them (ensure() does not
     // keep a buffer's contents when it grows)
-    int rc = alloc_points((int64_t)G * N, kmax);
+    rc = alloc_points((int64_t)G * N, mp.kmax);
     if (rc) return rc;
     const int nnodes3 = 2 << tree_depth_for(max_n);
     const size_t nbox = (size_t)G * nbase * nnodes3 * 3;
@@ -1117,27 +1129,13 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     // ---- shared setup (ISR.cpp:568-648) of the base clouds
     npairs_ = P;
     ntot_ = N;  // (ld_ stays the group's: the SoA columns keep one stride through the sweep)
+    // (alpha = beta = 1: the rows are weighted, and a cf target's f32 rows formed, per variant)
     std::vector<CloudReq> clouds(nbase);
-    for (int p = 0; p < P; ++p) {
-        for (int side = 0; side < 2; ++side) {
-            CloudReq& r = clouds[2 * p + side];
-            r.in = side == 0 ? src[p] : tgt[p];
-            r.n = side == 0 ? ns[p] : nt[p];
-            CloudSetup& st = r.st;
-            st = CloudSetup{};
-            st.k_lrf = k_lrf;
-            st.k_nrm = side == 0 ? k_nrm_s : k_nrm_t;
-            st.k_knn = std::max(st.k_lrf, st.k_nrm);
-            st.want_cov = mi.est == EST_GICP;
-            st.want_conf = mi.kind == KIND_CF;
-            st.is_target = side == 1;
-            st.cf_target = 0;  // (the rows are weighted, and a cf target's f32 rows formed, per variant)
-            st.alpha = 1.0;
-            st.beta = 1.0;
-            st.norm_scale = 1.0;
-        }
-    }
-    rc = setup_clouds(clouds, on_device, se3, prm0.scale_preprocessing, false, nullptr, nullptr, s);
+    for (int p = 0; p < P; ++p)
+        for (int side = 0; side < 2; ++side)
+            clouds[2 * p + side] = CloudReq{side == 0 ? src[p] : tgt[p], side == 0 ? ns[p] : nt[p],
+                                            cloud_setup(mp, side, 1.0, 1.0, false)};
+    rc = setup_clouds(clouds, on_device, true, se3, prm0.scale_preprocessing, s);
     if (rc) return rc;
     if (se3)
         HIPCHK(hipMemcpyAsync(d_raw_.p, d_fr64_.p, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
@@ -1171,7 +1169,7 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
                 CloudSetup st = base_setup[c];
                 st.alpha = w[k].alpha;
                 st.beta = w[k].beta;
-                st.cf_target = (mi.kind == KIND_CF && st.is_target) ? 1 : 0;
+                st.cf_target = (mp.kind == KIND_CF && st.is_target) ? 1 : 0;
                 h_setup_[k * nbase + c] = st;  // (host mirror; the device's is written by k_sweep_expand)
             }
         }
@@ -1182,7 +1180,7 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
         a.nclouds = nbase;
         a.nnodes3 = nnodes3;
         a.frames = se3 ? 1 : 0;
-        a.cf = mi.kind == KIND_CF ? 1 : 0;
+        a.cf = mp.kind == KIND_CF ? 1 : 0;
         a.raw = (const double*)d_raw_.p;
         a.w = (const SweepWeight*)d_sweep_w_.p;
         a.scales = se3 ? (double*)d_scales_.p : nullptr;
@@ -1195,19 +1193,6 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
         a.hi3 = (float*)t3_.hi.p;
         launch_sweep_expand(view(), a, s);
         HIPCHK(hipGetLastError());
-        have12_ = se3;
-        if (se3) {
-            rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
-            if (rc) return rc;
-        }
-        rc = prepare_pairs(g * P, vns.data(), vnt.data(), s);
-        if (rc) return rc;
-        rc = setup_chunks(g * P, s);
-        if (rc) return rc;
-        HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * ld_, s));  // no previous match yet
-        HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
-        for (double& t : trace_prev_) t = 0;
-        HIPCHK(hipEventRecord(ev_[13], s));
         // the armed trace, if its pair is in this group (result index v * P + p)
         se3icp_trace gtr{};
         se3icp_trace* use = nullptr;
@@ -1216,9 +1201,8 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
             gtr.pair = tr->pair - v0 * P;
             use = &gtr;
         }
-        const ReportReq rq{ropts, reports ? reports + (size_t)v0 * P : nullptr};
-        rc = run_loop(g * P, vns.data(), mi.kind, mi.est, variants + v0, P, true, use, out + (size_t)v0 * P, s,
-                      (ropts && reports) ? &rq : nullptr);
+        rc = run_pairs(mp, g * P, vns.data(), vnt.data(), variants + v0, P, true, Call{use, s}, out + (size_t)v0 * P,
+                       ropts, reports ? reports + (size_t)v0 * P : nullptr);
         if (use) tr->iters_recorded = gtr.iters_recorded;
         if (rc && rc != SE3ICP_ERR_NONFINITE) return rc;
         if (rc) worst = rc;
@@ -1237,8 +1221,7 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
 //   B  the 2P uses, as a batch lays them out: k_graph_normalize from A's raw columns and a 3-D
 //      tree for every use; kNN / frames / normals only for the first use of every class (the
 //      other uses ask for no neighbours, which the kernels skip); k_graph_share copies those
-//      to the class's other uses; then 12-D trees, prepare_pairs, setup_chunks and run_loop
-//      exactly as a batch.
+//      to the class's other uses; then run_pairs, as a batch.
 // A's raw columns are kept by swapping their buffer out for B's (memory is not saved: every
 // use is materialised, the loop's state lives at a use's slots).  A cloud sets up bitwise the
 // same at any position of any batch, so every result equals register_batch's for the expanded
@@ -1247,38 +1230,20 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
                            const int32_t* etgt, bool on_device, int method, const se3icp_params& prm, int sharing,
                            se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
                            se3icp_report* reports) {
-    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_trace* tr = trace_;  // one-shot: the record covers this call only (trace.pair: the edge)
-    trace_ = nullptr;
-    if (C <= 0 || P <= 0 || !xyz || !npts || !esrc || !etgt || !out) return SE3ICP_ERR_INVALID_ARG;
-    if (tr && (tr->pair < 0 || tr->pair >= P || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
-    if (tr) tr->iters_recorded = 0;
-    MethodInfo mi;
-    if (!decode_method(method, &mi)) return SE3ICP_ERR_INVALID_METHOD;
+    // ---- layouts A (used clouds, in cloud order) and B (uses)
+    const int args = (C <= 0 || P <= 0 || !xyz || !npts || !esrc || !etgt || !out) ? SE3ICP_ERR_INVALID_ARG : 0;
+    MethodPlan mp{};
+    std::vector<int32_t> slotA, cloudA;
+    int rest = args ? 0 : plan_method(method, prm.number_of_nn_for_LRF, &mp);
+    if (!args && !rest) rest = graph_used_clouds(C, xyz, npts, P, esrc, etgt, &slotA, &cloudA);
+    Call call;
+    int rc = open_call(args, P, rest, user_stream, &call);
+    if (rc) return rc;
+    hipStream_t s = call.s;
+    const bool se3 = mp.se3;
     if (sharing == 0) sharing = 3;
     // (level 3, neighbour-set adoption between the classes of a cloud, is not built: as 2)
-    const bool se3 = mi.kind != KIND_ICP;
-    const int k_lrf = se3 ? prm.number_of_nn_for_LRF : 0;
-    if (se3 && k_lrf <= 0) return SE3ICP_ERR_INVALID_ARG;
-    int k_nrm_s = 0, k_nrm_t = 0;
-    if (mi.est == EST_PT2PL) k_nrm_t = 30;
-    if (mi.est == EST_GICP) { k_nrm_s = 20; k_nrm_t = 20; }
-    const int kmax = std::max({k_lrf, k_nrm_s, k_nrm_t, 1});
     for (int64_t& g : graph_stats_) g = 0;
-
-    // ---- layouts A (used clouds, in cloud order) and B (uses)
-    std::vector<int32_t> slotA(C, -1), cloudA;
-    for (int p = 0; p < P; ++p) {
-        if (esrc[p] < 0 || esrc[p] >= C || etgt[p] < 0 || etgt[p] >= C) return SE3ICP_ERR_INVALID_ARG;
-        slotA[esrc[p]] = slotA[etgt[p]] = 0;
-    }
-    for (int c = 0; c < C; ++c)
-        if (slotA[c] == 0) {
-            if (npts[c] <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
-            if (!xyz[c]) return SE3ICP_ERR_INVALID_ARG;
-            slotA[c] = (int32_t)cloudA.size();
-            cloudA.push_back(c);
-        }
     const int CA = (int)cloudA.size();
     std::vector<int64_t> ns(P), nt(P);
     int64_t NA = 0, NU = 0;
@@ -1291,13 +1256,8 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
         nchU += (int)((ns[p] + kChunk - 1) / kChunk + (nt[p] + kChunk - 1) / kChunk);
     }
 
-    HIPCHK(hipSetDevice(dev_));
-    hipStream_t s = user_stream ? user_stream : stream_;
-    ktimes_ = KernelTimes{};
-    HIPCHK(hipEventRecord(ev_[12], s));
-
     // buffers of the larger layout first (NA <= NU points, and as many chunks at most)
-    int rc = alloc_points(NU, kmax);
+    rc = alloc_points(NU, mp.kmax);
     if (rc) return rc;
     const size_t L = (size_t)ld_;
     if (!ensure<CloudDev>(d_clouds_, 2 * (size_t)P) || !ensure<CloudSetup>(d_setup_, 2 * (size_t)P) ||
@@ -1305,42 +1265,22 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
         !ensure<double>(d_partial_, (size_t)nchU * 9) || !ensure<double>(d_centers_, 6 * (size_t)P) ||
         !ensure<double>(d_scales_, P) || !ensure<GraphSeg>(g_seg_, 2 * (size_t)P))
         return SE3ICP_ERR_OUT_OF_MEMORY;
-    if (pinned(h_partial_, h_partial_cap_, (size_t)nchU * 9 + 6 * (size_t)P + 8)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    if (h_partial_.reserve((size_t)nchU * 9 + 6 * (size_t)P + 8)) return SE3ICP_ERR_OUT_OF_MEMORY;
 
     // ---- A: every used cloud once
     npairs_ = 0;
-    nclouds_ = CA;
     ntot_ = NA;
-    std::vector<CloudDev> clA(CA);
-    std::vector<CloudSetup> stA(CA, CloudSetup{});
-    std::vector<ChunkWork> chA;
-    std::vector<const double*> inA(CA, nullptr);
-    {
-        int64_t off = 0;
-        for (int a = 0; a < CA; ++a) {
-            const int64_t n = npts[cloudA[a]];
-            clA[a] = CloudDev{(int32_t)off, (int32_t)n};
-            stA[a].want_conf = mi.kind == KIND_CF;
-            stA[a].alpha = stA[a].beta = stA[a].norm_scale = 1.0;
-            for (int64_t p0 = 0; p0 < n; p0 += kChunk) chA.push_back(ChunkWork{a, (int32_t)p0});
-            if (on_device) {
-                inA[a] = xyz[cloudA[a]];
-            } else {
-                double* dst = (double*)d_in_.p + 3 * (size_t)off;
-                HIPCHK(hipMemcpyAsync(dst, xyz[cloudA[a]], sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
-                inA[a] = dst;
-                graph_stats_[GS_BYTES_UPLOADED] += (int64_t)sizeof(double) * 3 * n;
-            }
-            off += n;
-        }
+    std::vector<CloudReq> reqA(CA);
+    for (int a = 0; a < CA; ++a) {
+        reqA[a] = CloudReq{xyz[cloudA[a]], npts[cloudA[a]], CloudSetup{}};
+        reqA[a].st.want_conf = mp.kind == KIND_CF;
+        reqA[a].st.alpha = reqA[a].st.beta = reqA[a].st.norm_scale = 1.0;
+        if (!on_device) graph_stats_[GS_BYTES_UPLOADED] += (int64_t)sizeof(double) * 3 * reqA[a].n;
     }
-    const int nchA = (int)chA.size();
-    h_clouds_ = clA;
-    h_setup_ = stA;
-    HIPCHK(hipMemcpyAsync(d_clouds_.p, clA.data(), sizeof(CloudDev) * CA, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_setup_.p, stA.data(), sizeof(CloudSetup) * CA, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_chunks_.p, chA.data(), sizeof(ChunkWork) * nchA, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_inptr_.p, inA.data(), sizeof(double*) * CA, hipMemcpyHostToDevice, s));
+    rc = upload_clouds(reqA, on_device, s);
+    if (rc) return rc;
+    const std::vector<CloudDev> clA = h_clouds_;
+    const int nchA = (int)h_chunks_.size();
     View v = view();
     launch_ingest(v, (const ChunkWork*)d_chunks_.p, nchA, (double*)d_partial_.p, s);
     HIPCHK(hipGetLastError());
@@ -1359,24 +1299,22 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
             for (int x = 0; x < 3; ++x) cenC[3 * (size_t)cloudA[a] + x] = h_partial_[3 * (size_t)a + x];
         for (int a = 0; a < CA; ++a) radC[cloudA[a]] = -1.0;
         for (int k = 0; k < nchA; ++k) {
-            double& r = radC[cloudA[chA[k].cloud]];
+            double& r = radC[cloudA[h_chunks_[k].cloud]];
             r = std::fmax(r, h_partial_[3 * (size_t)CA + k]);
         }
     } else {
-        // run_icp: the centroid as setup_clouds forms it on the host (chunk sums in order)
-        HIPCHK(hipMemcpyAsync(h_partial_, d_partial_.p, sizeof(double) * 9 * nchA, hipMemcpyDeviceToHost, s));
-        SYNC_STREAM(s);
-        std::vector<double> sum(3 * (size_t)CA, 0.0);
-        for (int k = 0; k < nchA; ++k)
-            for (int x = 0; x < 3; ++x) sum[3 * (size_t)chA[k].cloud + x] += h_partial_[9 * (size_t)k + x];
+        // run_icp: the centroid as setup_clouds forms it on the host
+        std::vector<double> cenA;
+        rc = host_centroids(s, &cenA);
+        if (rc) return rc;
         for (int a = 0; a < CA; ++a)
-            for (int x = 0; x < 3; ++x) cenC[3 * (size_t)cloudA[a] + x] = sum[3 * (size_t)a + x] / (double)clA[a].n;
+            for (int x = 0; x < 3; ++x) cenC[3 * (size_t)cloudA[a] + x] = cenA[3 * (size_t)a + x];
     }
 
     // ---- classes
     GraphPlan plan;
-    graph_plan(P, esrc, etgt, se3, prm.scale_preprocessing, cenC.data(), radC.data(), k_nrm_s, k_nrm_t, sharing >= 2,
-               &plan);
+    graph_plan(P, esrc, etgt, se3, prm.scale_preprocessing, cenC.data(), radC.data(), mp.k_nrm_s, mp.k_nrm_t,
+               sharing >= 2, &plan);
     const int K = (int)plan.classes.size();
     graph_stats_[GS_CLOUDS] = CA;
     graph_stats_[GS_USES] = 2 * (int64_t)P;
@@ -1410,17 +1348,7 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
             const GraphClass& gc = plan.classes[plan.use_class[u]];
             const int64_t n = npts[gc.cloud];
             clU[u] = CloudDev{(int32_t)off, (int32_t)n};
-            CloudSetup& st = stU[u];
-            st = CloudSetup{};
-            st.k_lrf = k_lrf;
-            st.k_nrm = side == 0 ? k_nrm_s : k_nrm_t;
-            st.k_knn = std::max(st.k_lrf, st.k_nrm);
-            st.want_cov = mi.est == EST_GICP;
-            st.want_conf = mi.kind == KIND_CF;
-            st.is_target = side;
-            st.cf_target = (mi.kind == KIND_CF && side == 1) ? 1 : 0;
-            st.alpha = prm.alpha_rot;
-            st.beta = prm.beta_transl;
+            CloudSetup& st = stU[u] = cloud_setup(mp, side, prm.alpha_rot, prm.beta_transl, true);
             for (int x = 0; x < 3; ++x) {
                 st.norm_center[x] = gc.norm_center[x];
                 st.f32_center[x] = gc.f32_center[x];
@@ -1442,7 +1370,7 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
             CloudSetup& st = stRun[u];
             st = stU[u];
             const bool is_home = home[k] == u;
-            st.k_lrf = is_home ? k_lrf : 0;
+            st.k_lrf = is_home ? mp.k_lrf : 0;
             st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
             st.k_knn = std::max(st.k_lrf, st.k_nrm);
             graph_stats_[GS_FULL] += st.k_knn > 0;
@@ -1482,21 +1410,7 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
         launch_graph_share(view(), (const ChunkWork*)g_chunks_.p, nchS, (const GraphSeg*)g_seg_.p, s);
         HIPCHK(hipGetLastError());
     }
-    have12_ = se3;
-    if (se3) {
-        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
-        if (rc) return rc;
-    }
-    rc = prepare_pairs(P, ns.data(), nt.data(), s);
-    if (rc) return rc;
-    rc = setup_chunks(P, s);
-    if (rc) return rc;
-    HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * ld_, s));  // no previous match yet
-    HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
-    for (double& t : trace_prev_) t = 0;
-    HIPCHK(hipEventRecord(ev_[13], s));
-    const ReportReq rq{ropts, reports};
-    return run_loop(P, ns.data(), mi.kind, mi.est, &prm, P, false, tr, out, s, (ropts && reports) ? &rq : nullptr);
+    return run_pairs(mp, P, ns.data(), nt.data(), &prm, P, false, call, out, ropts, reports);
 }
 
 // Row it-1 of the armed trace after iteration `it` completed (the stream is idle: the
@@ -1550,7 +1464,7 @@ int Engine::knn_self(const double* xyz, int64_t n, int k, int32_t* idx) {
     cl[0].n = n;
     cl[0].st.k_knn = k;
     cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, 1.0, false, nullptr, nullptr, stream_);
+    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(idx, sizeof(int32_t) * k, d_knn_.p, sizeof(int32_t) * kmax_, sizeof(int32_t) * k, n,
                             hipMemcpyDeviceToHost, stream_));
@@ -1574,7 +1488,7 @@ int Engine::toldi_frames(const double* xyz, int64_t n, int k, double* frames) {
     cl[0].st.alpha = 1.0;
     cl[0].st.beta = 1.0;
     cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, 1.0, false, nullptr, nullptr, stream_);
+    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
     if (rc) return rc;
     std::vector<double> fr(12 * (size_t)ld_);
     HIPCHK(hipMemcpyAsync(fr.data(), d_fr64_.p, sizeof(double) * 12 * ld_, hipMemcpyDeviceToHost, stream_));
@@ -1606,7 +1520,7 @@ int Engine::estimate_normals(const double* xyz, int64_t n, int k, double* normal
     cl[0].st.k_knn = k;
     cl[0].st.k_nrm = k;
     cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, 1.0, false, nullptr, nullptr, stream_);
+    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
     if (rc) return rc;
     std::vector<double> nr(3 * (size_t)ld_);
     HIPCHK(hipMemcpyAsync(nr.data(), d_nrm64_.p, sizeof(double) * 3 * ld_, hipMemcpyDeviceToHost, stream_));

@@ -19,9 +19,33 @@
 
 namespace se3icp {
 
+// A device buffer (Engine::ensure) and a pinned host mirror.  Each names the engine's list it
+// belongs to when it is declared: the destructor and the sweep's memory count walk those
+// lists, so a new member cannot be left out of them.
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    explicit DevBuf(std::vector<DevBuf*>& owner) { owner.push_back(this); }
+};
+struct PinnedMem {
+    void* mem = nullptr;
+    size_t cap = 0;  // elements
+};
+template <class T>
+struct Pinned : PinnedMem {
+    explicit Pinned(std::vector<PinnedMem*>& owner) { owner.push_back(this); }
+    operator T*() const { return static_cast<T*>(mem); }
+    // room for `count` elements (at least 16); growing frees first, the contents are not kept
+    int reserve(size_t count) {
+        if (cap >= count && mem) return 0;
+        if (mem) (void)hipHostFree(mem);
+        mem = nullptr;
+        cap = 0;
+        const size_t want = count > 16 ? count : 16;
+        if (hipHostMalloc(&mem, want * sizeof(T), hipHostMallocDefault) != hipSuccess) return SE3ICP_ERR_OUT_OF_MEMORY;
+        cap = want;
+        return 0;
+    }
 };
 
 // Per-kernel GPU time of the last register_batch (HIP events, ms), for bench.py.
@@ -39,6 +63,14 @@ struct KernelTimes {
     // NN certificates (k_nn_prep): its time, and per phase the queries of all iterations
     // and those that had to be searched
     double nn_prep_ms = 0, se3_queries = 0, se3_searched = 0, r3_queries = 0, r3_searched = 0;
+};
+
+// What a method asks of the setup and the loop (plan_method, engine.cpp).
+struct MethodPlan {
+    Kind kind;
+    int est;
+    bool se3;                            // an SE(3) method: frames, 12-D trees, normalized pairs
+    int k_lrf, k_nrm_s, k_nrm_t, kmax;   // TOLDI k, normals k of sources / targets, the largest
 };
 
 class Engine {
@@ -93,6 +125,8 @@ class Engine {
     struct TreeBufs {
         DevBuf perm, pos, vec, vec64, vec64a, blo, bhi, lo, hi, scr, vecT;  // (vecT: 12-D input columns)
         int L = 0;  // depth of the trees in these buffers
+        explicit TreeBufs(std::vector<DevBuf*>& o)
+            : perm(o), pos(o), vec(o), vec64(o), vec64a(o), blo(o), bhi(o), lo(o), hi(o), scr(o), vecT(o) {}
     };
     int init();
     template <class T>
@@ -100,21 +134,45 @@ class Engine {
     int alloc_points(int64_t ntot, int kmax, bool knn_list = false);
     // build the D-dimensional kd-trees of every cloud over `vec` ([D][ld] f32)
     int build_tree(int D, const float* vec, hipStream_t s, const double* vec64 = nullptr);
-    // ingest -> (normalize) -> 3-D kd-trees -> kNN -> frames (-> 12-D kd-trees) for a
-    // list of clouds.  When `normalize_pairs` is set, clouds (2p, 2p+1) are normalized
-    // together with the reference's preprocessing and scale[p] receives the factor.
-    int setup_clouds(std::vector<CloudReq>& clouds, bool on_device, bool normalize_pairs, double scale_pre,
-                     bool build12, std::vector<double>* centers, std::vector<double>* scales, hipStream_t s);
+    // A registration call (register_batch, each group of register_sweep, register_graph) is
+    // open_call, the entry's own setup of its clouds, and run_pairs.
+    //
+    // open_call: the engine check, the armed trace (taken, and so disarmed, even when the call
+    // is then rejected) validated against the call's `nslots` result slots, the device, the
+    // stream, the kernel times' reset and the begin event.  The entry's own argument checks
+    // surround the trace's: `args` is the status of those before it, `rest` (evaluated by the
+    // entry only when `args` is 0) of those after it.
+    struct Call {
+        se3icp_trace* tr = nullptr;
+        hipStream_t s = nullptr;
+    };
+    int open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c);
+    // The clouds back to back in the SoA columns: offsets, chunk list, inputs (uploaded, or
+    // pointed at when on_device) and the cloud, setup, chunk and input tables on the device.
+    int upload_clouds(const std::vector<CloudReq>& clouds, bool on_device, hipStream_t s);
+    // every cloud's centroid from k_ingest's chunk sums on the host: chunks in order, then / n
+    int host_centroids(hipStream_t s, std::vector<double>* cen);
+    // upload_clouds -> ingest -> normalize -> 3-D kd-trees -> kNN -> frames for a list of
+    // clouds.  pairs: clouds (2p, 2p+1) are source and target of pair p (otherwise every cloud
+    // stands alone); normalize (pairs only): they are normalized together with the
+    // reference's preprocessing, the centers and scale[p] staying on the device.
+    int setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bool pairs, bool normalize, double scale_pre,
+                     hipStream_t s);
     // kNN / frames / normals of the clouds set up so far (step 4 of setup_clouds)
     int setup_knn(hipStream_t s);
     int setup_chunks(int npairs, hipStream_t s);
-    // the two halves of a registration around setup_clouds.  prepare_pairs: the work table
-    // of k_reduce and the per-pair buffers of a batch of npairs pairs laid out src 0, tgt 0,
-    // src 1, ...; run_loop: loop state, the loop and the results of those pairs.  Pair q
-    // takes its parameters from vprm[q / pairs_per_variant] (a plain batch: one variant of
-    // npairs pairs; a sweep group: the group's variants, pair q a replica of base pair
+    // run_pairs: everything behind the clouds' setup, for npairs pairs laid out src 0, tgt 0,
+    // src 1, ...: the 12-D kd-trees over the weighted SE(3) elements (SE(3) methods),
+    // prepare_pairs (the work table of k_reduce and the per-pair buffers), setup_chunks, the
+    // loop's cleared buffers, the setup-done event and run_loop (loop state, the loop, the
+    // results and, with `ropts` and `reports`, the report of every pair).  Pair q takes its
+    // parameters from vprm[q / pairs_per_variant] (a plain batch: one variant of npairs pairs;
+    // a sweep group: the group's variants, pair q a replica of base pair
     // q % pairs_per_variant).  sweep: the setup time is the shared setup's (events 12 -> 8)
     // plus the group's (9 -> 13) instead of 12 -> 13.
+    int run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const int64_t* nt,
+                  const se3icp_params* vprm, int pairs_per_variant, bool sweep, const Call& c, se3icp_result* out,
+                  const se3icp_report_options* ropts, se3icp_report* reports);
     int prepare_pairs(int npairs, const int64_t* ns, const int64_t* nt, hipStream_t s);
     // rq (may be null): the registration report of every pair, evaluated after the loop
     struct ReportReq {
@@ -126,7 +184,6 @@ class Engine {
     // queue the report stage behind the loop (k_report.hip): an R3 search at the final poses,
     // the per-pair sums into h_rep_, the per-point outputs into the caller's buffers
     int queue_report(int npairs, const int64_t* ns, const ReportReq& rq, hipStream_t s);
-    std::vector<DevBuf*> all_bufs();
     int read_lrf_stats();
     int sync_stream(hipStream_t s);
     View view() const;
@@ -143,7 +200,7 @@ class Engine {
     int64_t ntot_ = 0;
     int ld_ = 0, kmax_ = 1, nwork_ = 0, tree_L_ = 0;
     int chunk_level_ = 0, nchunks_ = 0;  // loop NN work chunks (View::chunk_level)
-    bool have12_ = false, knn_list_ = false;
+    bool knn_list_ = false;
     bool nn_trace_ = false;              // SE3ICP_NN_TRACE=1: per-iteration NN work on stderr
     // se3icp_set_lrf_exact: 0 k_lrf8 + hand-overs (default), 1 the exact one-query-per-wavefront
     // k_lrf for every point, 2 the global-buffer k_knn_big for every point (all bitwise equal)
@@ -162,41 +219,42 @@ class Engine {
     std::vector<ChunkWork> h_chunks_;
     std::vector<const double*> h_inptr_;
 
-    // device buffers
-    DevBuf d_clouds_, d_setup_, d_pairs_, d_cloud_of_, d_inptr_, d_in_, d_xyz64_, d_xyz32_, d_fr64_, d_fr32_, d_nrm64_, d_tgeo_,
-        d_conf64_, d_knn_, d_corr_idx_, d_corr_dist_, d_flag_count_, d_gcost_, d_cls_,
-        d_trim_key_, d_red_partial_, d_red_out_, d_work_, d_wb_, d_wn_, d_chunks_, d_partial_, d_centers_,
-        d_rechecked_, d_keys0_, d_vals1_, d_sort_tmp_, d_stats_, d_qlist_, d_qcount_, d_hist_, d_cert_,
-        d_sqlist_, d_state_, d_trim_cand_, d_trim_ctr_, d_scales_, d_trim_hist_,
-        d_lrf_fb_, d_lrf_fbn_,  // k_lrf8 -> exact k_lrf hand-over list and its count
-        d_big_d_, d_big_i_,     // k_knn_big candidate buffers (neighbourhoods over kSmallK)
-        d_raw_, d_sweep_w_,     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
-        d_rep_partial_, d_rep_out_, d_rep_off_, d_rep_idx_, d_rep_dist_;  // the report's sums and per-point staging
-    TreeBufs t3_, t12_;
+    // device buffers and pinned host mirrors: each is named here and nowhere else (bufs_ and
+    // pins_, declared first, collect them as they are constructed)
+    std::vector<DevBuf*> bufs_;
+    std::vector<PinnedMem*> pins_;
+    DevBuf d_clouds_{bufs_}, d_setup_{bufs_}, d_pairs_{bufs_}, d_cloud_of_{bufs_}, d_inptr_{bufs_}, d_in_{bufs_},
+        d_xyz64_{bufs_}, d_xyz32_{bufs_}, d_fr64_{bufs_}, d_fr32_{bufs_}, d_nrm64_{bufs_}, d_tgeo_{bufs_},
+        d_conf64_{bufs_}, d_knn_{bufs_}, d_corr_idx_{bufs_}, d_corr_dist_{bufs_}, d_flag_count_{bufs_},
+        d_gcost_{bufs_}, d_cls_{bufs_}, d_trim_key_{bufs_}, d_red_partial_{bufs_}, d_red_out_{bufs_}, d_work_{bufs_},
+        d_wb_{bufs_}, d_wn_{bufs_}, d_chunks_{bufs_}, d_partial_{bufs_}, d_centers_{bufs_}, d_rechecked_{bufs_},
+        d_keys0_{bufs_}, d_vals1_{bufs_}, d_sort_tmp_{bufs_}, d_stats_{bufs_}, d_qlist_{bufs_}, d_qcount_{bufs_},
+        d_hist_{bufs_}, d_cert_{bufs_}, d_sqlist_{bufs_}, d_state_{bufs_}, d_trim_cand_{bufs_}, d_trim_ctr_{bufs_},
+        d_scales_{bufs_}, d_trim_hist_{bufs_},
+        d_lrf_fb_{bufs_}, d_lrf_fbn_{bufs_},  // k_lrf8 -> exact k_lrf hand-over list and its count
+        d_big_d_{bufs_}, d_big_i_{bufs_},     // k_knn_big candidate buffers (neighbourhoods over kSmallK)
+        d_raw_{bufs_}, d_sweep_w_{bufs_},     // register_sweep: unweighted SE(3) rows of the shared setup, a group's weights
+        // the report's sums and per-point staging
+        d_rep_partial_{bufs_}, d_rep_out_{bufs_}, d_rep_off_{bufs_}, d_rep_idx_{bufs_}, d_rep_dist_{bufs_};
+    TreeBufs t3_{bufs_}, t12_{bufs_};
     // register_graph: the distinct clouds' raw columns and confidences (swapped with xyz64 /
     // conf64 between the call's two layouts), the segment and chunk tables of the k_graph kernels
-    DevBuf g_raw_xyz_, g_raw_conf_, g_seg_, g_chunks_;
+    DevBuf g_raw_xyz_{bufs_}, g_raw_conf_{bufs_}, g_seg_{bufs_}, g_chunks_{bufs_};
     int64_t graph_stats_[9] = {};
-    // pinned host mirrors
-    PairDev* h_pairs_ = nullptr;
-    double* h_red_ = nullptr;
-    double* h_partial_ = nullptr;
-    int32_t* h_rechecked_ = nullptr;
-    double* h_hist_ = nullptr;  // one pose-history row (npairs x 12)
-    double* h_rep_ = nullptr;   // the report's sums (npairs x kRepVals)
-    size_t h_rep_cap_ = 0;
+    Pinned<PairDev> h_pairs_{pins_};
+    Pinned<double> h_red_{pins_}, h_partial_{pins_};
+    Pinned<int32_t> h_rechecked_{pins_};
+    Pinned<double> h_hist_{pins_};  // one pose-history row (npairs x 12)
+    Pinned<double> h_rep_{pins_};   // the report's sums (npairs x kRepVals)
     std::vector<int64_t> h_rep_off_;  // first per-point output entry of each pair
-    size_t h_pairs_cap_ = 0, h_red_cap_ = 0, h_partial_cap_ = 0, h_rechecked_cap_ = 0, h_hist_cap_ = 0;
-    PairState* h_state_ = nullptr;  // loop state of every pair (read back after the loop)
+    Pinned<PairState> h_state_{pins_};  // loop state of every pair (read back after the loop)
     // [kLoopRing][npairs] each pair's phase in the next iteration, written by k_reduce_final
     // into coherent host memory (h_phase_ host view, d_phase_ device view)
     int32_t* h_phase_ = nullptr;
     int32_t* d_phase_ = nullptr;
-    size_t h_state_cap_ = 0, h_phase_cap_ = 0;
-    unsigned long long* h_lrf_stats_ = nullptr;  // k_lrf work counters (read at the next sync)
-    size_t h_lrf_stats_cap_ = 0;
-    unsigned long long* h_loop_stats_ = nullptr;  // loop NN work counters (pinned: an async copy, not a staged one)
-    size_t h_loop_stats_cap_ = 0;
+    size_t h_phase_cap_ = 0;
+    Pinned<unsigned long long> h_lrf_stats_{pins_};   // k_lrf work counters (read at the next sync)
+    Pinned<unsigned long long> h_loop_stats_{pins_};  // loop NN work counters (pinned: an async copy, not a staged one)
     bool lrf_stats_pending_ = false;
     // 6/7: k_lrf time; 12/13/14: batch begin / setup done / loop done (GPU-timeline phase
     // times); 8/9: a sweep's shared setup done / group begin; 15: sync_stream; the rest unused

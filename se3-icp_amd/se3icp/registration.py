@@ -15,6 +15,7 @@ examples/benchmark_kitti.cpp:120-197 and examples/benchmark_lounge.cpp:154-235.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import threading
 import time
@@ -218,22 +219,62 @@ def lounge_params(**overrides) -> _lib.Params:
     return p
 
 
-def register_batch(pairs, method: str, params: _lib.Params | None = None, device: int = 0) -> list[PairResult]:
-    """Register [(src (N,3), tgt (M,3)), ...] in lockstep on one GPU (host buffers)."""
-    L = _lib.load()
+# ---- marshalling shared by the register_* functions below
+_DP = C.POINTER(C.c_double)
+
+
+def _pair_args(pairs):
+    """(n, the four pointer / size arguments of a host entry, the source sizes, the arrays
+    those point into: the caller holds them until the call has returned)."""
     srcs = [_as_xyz(s) for s, _ in pairs]
     tgts = [_as_xyz(t) for _, t in pairs]
     n = len(pairs)
-    dp = C.POINTER(C.c_double)
-    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
-    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
-    ns = (C.c_int64 * n)(*[a.shape[0] for a in srcs])
-    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
-    res = (_lib.Result * n)()
-    rc = L.se3icp_register_batch(device, n, sp, ns, tp, nt, _lib.method_id(method),
-                                 C.byref(params or _lib.default_params()), res)
+    counts = [a.shape[0] for a in srcs]
+    args = ((_DP * n)(*[a.ctypes.data_as(_DP) for a in srcs]), (C.c_int64 * n)(*counts),
+            (_DP * n)(*[a.ctypes.data_as(_DP) for a in tgts]), (C.c_int64 * n)(*[a.shape[0] for a in tgts]))
+    return n, args, counts, (srcs, tgts)
+
+
+def _offset_args(src_ptr: int, src_off, tgt_ptr: int, tgt_off):
+    """(n, the four pointer / offset arguments of a *_device entry)."""
+    n = len(src_off) - 1
+    return n, (C.c_void_p(src_ptr), (C.c_int64 * (n + 1))(*[int(x) for x in src_off]),
+               C.c_void_p(tgt_ptr), (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off]))
+
+
+def _cloud_args(clouds):
+    """(the (N, 3) arrays of a cloud set, the count / pointer / size arguments of a graph entry)."""
+    cl = [_as_xyz(c) for c in clouds]
+    nc = len(cl)
+    return cl, (nc, (_DP * max(nc, 1))(*[a.ctypes.data_as(_DP) for a in cl]),
+                (C.c_int64 * max(nc, 1))(*[a.shape[0] for a in cl]))
+
+
+def _outputs(n):
+    """Result and report arrays of n slots (one at least: the C side is never handed an empty array)."""
+    return (_lib.Result * max(1, n))(), (_lib.Report * max(1, n))()
+
+
+def _params_ref(params):
+    return C.byref(params or _lib.default_params())
+
+
+def _stream_arg(stream: int):
+    return C.c_void_p(stream) if stream else None
+
+
+def _registered(rc: int, what: str) -> None:
+    """Raise unless the call ran (a non-finite pose is a pair's status, not the call's failure)."""
     if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_batch")
+        raise _lib.Se3IcpError(rc, what)
+
+
+def register_batch(pairs, method: str, params: _lib.Params | None = None, device: int = 0) -> list[PairResult]:
+    """Register [(src (N,3), tgt (M,3)), ...] in lockstep on one GPU (host buffers)."""
+    n, args, _, _keep = _pair_args(pairs)
+    res, _ = _outputs(n)
+    _registered(_lib.load().se3icp_register_batch(device, n, *args, _lib.method_id(method), _params_ref(params), res),
+                "register_batch")
     return _results(res, n)
 
 
@@ -244,16 +285,10 @@ def register_batch_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: 
     src_ptr/tgt_ptr: device addresses of the concatenated AoS float64 xyz arrays
     (e.g. ``torch_tensor.data_ptr()``); src_off/tgt_off: n_pairs+1 point offsets.
     """
-    L = _lib.load()
-    n = len(src_off) - 1
-    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
-    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
-    res = (_lib.Result * n)()
-    rc = L.se3icp_register_batch_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
-                                        _lib.method_id(method), C.byref(params or _lib.default_params()), res,
-                                        C.c_void_p(stream) if stream else None)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_batch_device")
+    n, args = _offset_args(src_ptr, src_off, tgt_ptr, tgt_off)
+    res, _ = _outputs(n)
+    _registered(_lib.load().se3icp_register_batch_device(device, n, *args, _lib.method_id(method), _params_ref(params),
+                                                         res, _stream_arg(stream)), "register_batch_device")
     return _results(res, n)
 
 
@@ -374,29 +409,38 @@ class PipelinedBatchRunner:
         return self._runners[self._owner[s]].kernel_times(s)
 
 
+@contextlib.contextmanager
+def _armed_trace(device: int, slot: int, n_src: int, max_iters: int):
+    """Arm the per-iteration record of result slot `slot` (a source of n_src points) for the one
+    registration call made inside the block; the dict it yields holds, after the block, the
+    recorded arrays cut to the recorded iterations."""
+    L = _lib.load()
+    tr = {"corr_idx": np.full((max_iters, n_src), -1, np.int32), "corr_dist": np.zeros((max_iters, n_src), np.float32),
+          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
+          "phase": np.zeros(max_iters, np.int32)}
+    t = _lib.Trace(slot, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
+                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
+                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(_DP),
+                   tr["mse"].ctypes.data_as(_DP), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)), 0, 0)
+    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
+    trace = {}
+    try:
+        yield trace
+    finally:
+        L.se3icp_set_trace(device, None)
+    n = int(t.iters_recorded)
+    trace.update({k: v[:n] for k, v in tr.items()})
+
+
 def register_batch_traced(pairs, method: str, params: _lib.Params | None = None, pair: int = 0,
                           max_iters: int = 160, device: int = 0):
     """register_batch with the per-iteration record of one pair (se3icp_set_trace): the
     pre-trim correspondence set (target index, float distance) of every iteration, the
     trimmed rejector's cut, the pose and the MSE after it and the phase it ran in.
     Returns (results, trace dict with arrays cut to the recorded iterations)."""
-    L = _lib.load()
-    ns = _as_xyz(pairs[pair][0]).shape[0]
-    tr = {"corr_idx": np.full((max_iters, ns), -1, np.int32), "corr_dist": np.zeros((max_iters, ns), np.float32),
-          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
-          "phase": np.zeros(max_iters, np.int32)}
-    t = _lib.Trace(pair, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
-                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(C.POINTER(C.c_double)),
-                   tr["mse"].ctypes.data_as(C.POINTER(C.c_double)), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   0, 0)
-    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
-    try:
+    with _armed_trace(device, pair, _as_xyz(pairs[pair][0]).shape[0], max_iters) as trace:
         res = register_batch(pairs, method, params, device)
-    finally:
-        L.se3icp_set_trace(device, None)
-    n = int(t.iters_recorded)
-    return res, {k: v[:n] for k, v in tr.items()}
+    return res, trace
 
 
 # ---- parameter sweeps (the outer loop of the reference's benchmark drivers)
@@ -441,11 +485,12 @@ def sweep_params(base: _lib.Params | None = None, **lists) -> list[_lib.Params]:
 
 
 def _variant_array(variants):
+    """(the number of variants, their array; NULL for none)."""
     nv = len(variants)
     arr = (_lib.Params * nv)()
     for i, p in enumerate(variants):
         C.memmove(C.byref(arr, i * C.sizeof(_lib.Params)), C.byref(p), C.sizeof(_lib.Params))
-    return arr
+    return nv, (arr if nv else None)
 
 
 def _sweep_results(res, nv, n) -> list[list[PairResult]]:
@@ -458,36 +503,22 @@ def register_sweep(pairs, method: str, variants, device: int = 0, max_group: int
     share number_of_nn_for_LRF and scale_preprocessing) with one shared setup; result
     ``[v][p]`` is bitwise what ``register_batch(pairs, method, variants[v])[p]`` returns.
     max_group: variants registered in lockstep at once (0: the engine's choice)."""
-    L = _lib.load()
-    srcs = [_as_xyz(s) for s, _ in pairs]
-    tgts = [_as_xyz(t) for _, t in pairs]
-    n, nv = len(pairs), len(variants)
-    dp = C.POINTER(C.c_double)
-    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
-    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
-    ns = (C.c_int64 * n)(*[a.shape[0] for a in srcs])
-    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
-    res = (_lib.Result * max(1, nv * n))()
-    rc = L.se3icp_register_sweep(device, n, sp, ns, tp, nt, _lib.method_id(method), nv,
-                                 _variant_array(variants) if nv else None, max_group, res)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_sweep")
+    n, args, _, _keep = _pair_args(pairs)
+    nv, var = _variant_array(variants)
+    res, _ = _outputs(nv * n)
+    _registered(_lib.load().se3icp_register_sweep(device, n, *args, _lib.method_id(method), nv, var, max_group, res),
+                "register_sweep")
     return _sweep_results(res, nv, n)
 
 
 def register_sweep_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str, variants, device: int = 0,
                           stream: int = 0, max_group: int = 0) -> list[list[PairResult]]:
     """register_sweep for clouds already in HBM (arguments as register_batch_device)."""
-    L = _lib.load()
-    n, nv = len(src_off) - 1, len(variants)
-    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
-    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
-    res = (_lib.Result * max(1, nv * n))()
-    rc = L.se3icp_register_sweep_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
-                                        _lib.method_id(method), nv, _variant_array(variants) if nv else None,
-                                        max_group, res, C.c_void_p(stream) if stream else None)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_sweep_device")
+    n, args = _offset_args(src_ptr, src_off, tgt_ptr, tgt_off)
+    nv, var = _variant_array(variants)
+    res, _ = _outputs(nv * n)
+    _registered(_lib.load().se3icp_register_sweep_device(device, n, *args, _lib.method_id(method), nv, var, max_group,
+                                                         res, _stream_arg(stream)), "register_sweep_device")
     return _sweep_results(res, nv, n)
 
 
@@ -495,23 +526,9 @@ def register_sweep_traced(pairs, method: str, variants, variant: int = 0, pair: 
                           device: int = 0, max_group: int = 0):
     """register_sweep with the per-iteration record of pair ``pair`` under variant ``variant``
     (see register_batch_traced).  Returns (results, trace dict)."""
-    L = _lib.load()
-    ns = _as_xyz(pairs[pair][0]).shape[0]
-    tr = {"corr_idx": np.full((max_iters, ns), -1, np.int32), "corr_dist": np.zeros((max_iters, ns), np.float32),
-          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
-          "phase": np.zeros(max_iters, np.int32)}
-    t = _lib.Trace(variant * len(pairs) + pair, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
-                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(C.POINTER(C.c_double)),
-                   tr["mse"].ctypes.data_as(C.POINTER(C.c_double)), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   0, 0)
-    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
-    try:
+    with _armed_trace(device, variant * len(pairs) + pair, _as_xyz(pairs[pair][0]).shape[0], max_iters) as trace:
         res = register_sweep(pairs, method, variants, device, max_group)
-    finally:
-        L.se3icp_set_trace(device, None)
-    n = int(t.iters_recorded)
-    return res, {k: v[:n] for k, v in tr.items()}
+    return res, trace
 
 
 # ---- registration reports (fitness, RMSE, information matrix and final matches per pair)
@@ -542,10 +559,20 @@ def _report_options(max_correspondence_distance: float, idx_ptr=None, dist_ptr=N
     return _lib.ReportOptions(float(max_correspondence_distance), idx_ptr, dist_ptr, 1 if on_device else 0, 0)
 
 
-def _split(arr, counts):
+def _per_point_options(max_correspondence_distance: float, counts, per_point: bool):
+    """(report options, the per-point match and distance buffers they point at -- None without
+    per_point) for pairs of `counts` source points."""
+    idx = np.full(sum(counts), -1, np.int32) if per_point else None
+    dist = np.zeros(sum(counts)) if per_point else None
+    return _report_options(max_correspondence_distance, idx.ctypes.data if per_point else None,
+                           dist.ctypes.data if per_point else None), idx, dist
+
+
+def _pair_reports(rep, counts, idx=None, dist=None) -> list[PairReport]:
+    """One PairReport per pair, each with its own stretch of the per-point buffers (if any)."""
     out, at = [], 0
-    for n in counts:
-        out.append(arr[at:at + n])
+    for i, n in enumerate(counts):
+        out.append(_report(rep[i], None if idx is None else idx[at:at + n], None if dist is None else dist[at:at + n]))
         at += n
     return out
 
@@ -556,29 +583,12 @@ def register_batch_report(pairs, method: str, params: _lib.Params | None = None,
     (results, reports); the results are bitwise register_batch's.  A distance <= 0 or inf makes
     every point an inlier.  per_point: also the final match and its distance of every source
     point (PairReport.corr_idx / corr_dist)."""
-    L = _lib.load()
-    srcs = [_as_xyz(s) for s, _ in pairs]
-    tgts = [_as_xyz(t) for _, t in pairs]
-    n = len(pairs)
-    dp = C.POINTER(C.c_double)
-    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
-    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
-    counts = [a.shape[0] for a in srcs]
-    ns = (C.c_int64 * n)(*counts)
-    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
-    res = (_lib.Result * n)()
-    rep = (_lib.Report * n)()
-    idx = np.full(sum(counts), -1, np.int32) if per_point else None
-    dist = np.zeros(sum(counts)) if per_point else None
-    opts = _report_options(max_correspondence_distance, idx.ctypes.data if per_point else None,
-                           dist.ctypes.data if per_point else None)
-    rc = L.se3icp_register_batch_report(device, n, sp, ns, tp, nt, _lib.method_id(method),
-                                        C.byref(params or _lib.default_params()), res, C.byref(opts), rep)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_batch_report")
-    ii = _split(idx, counts) if per_point else [None] * n
-    dd = _split(dist, counts) if per_point else [None] * n
-    return _results(res, n), [_report(rep[i], ii[i], dd[i]) for i in range(n)]
+    n, args, counts, _keep = _pair_args(pairs)
+    res, rep = _outputs(n)
+    opts, idx, dist = _per_point_options(max_correspondence_distance, counts, per_point)
+    _registered(_lib.load().se3icp_register_batch_report(device, n, *args, _lib.method_id(method), _params_ref(params),
+                                                         res, C.byref(opts), rep), "register_batch_report")
+    return _results(res, n), _pair_reports(rep, counts, idx, dist)
 
 
 def register_batch_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str,
@@ -589,18 +599,12 @@ def register_batch_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, m
     corr_dist_ptr: optional addresses of int32 / float64 buffers of sum(n_src) entries (pair p
     at src_off[p] - src_off[0]) that receive the final matches -- device addresses (e.g.
     ``torch_tensor.data_ptr()``) when outputs_on_device, host addresses otherwise."""
-    L = _lib.load()
-    n = len(src_off) - 1
-    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
-    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
-    res = (_lib.Result * n)()
-    rep = (_lib.Report * n)()
+    n, args = _offset_args(src_ptr, src_off, tgt_ptr, tgt_off)
+    res, rep = _outputs(n)
     opts = _report_options(max_correspondence_distance, corr_idx_ptr or None, corr_dist_ptr or None, outputs_on_device)
-    rc = L.se3icp_register_batch_report_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
-                                               _lib.method_id(method), C.byref(params or _lib.default_params()), res,
-                                               C.c_void_p(stream) if stream else None, C.byref(opts), rep)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_batch_report_device")
+    _registered(_lib.load().se3icp_register_batch_report_device(device, n, *args, _lib.method_id(method),
+                                                                _params_ref(params), res, _stream_arg(stream),
+                                                                C.byref(opts), rep), "register_batch_report_device")
     return _results(res, n), [_report(rep[i]) for i in range(n)]
 
 
@@ -612,41 +616,25 @@ def register_sweep_report(pairs, method: str, variants, device: int = 0, max_gro
                           max_correspondence_distance: float = 0.0):
     """register_sweep plus reports: returns (results[v][p], reports[v][p]), e.g. to pick the
     alpha_rot of a sweep by fitness where there is no ground truth."""
-    L = _lib.load()
-    srcs = [_as_xyz(s) for s, _ in pairs]
-    tgts = [_as_xyz(t) for _, t in pairs]
-    n, nv = len(pairs), len(variants)
-    dp = C.POINTER(C.c_double)
-    sp = (dp * n)(*[a.ctypes.data_as(dp) for a in srcs])
-    tp = (dp * n)(*[a.ctypes.data_as(dp) for a in tgts])
-    ns = (C.c_int64 * n)(*[a.shape[0] for a in srcs])
-    nt = (C.c_int64 * n)(*[a.shape[0] for a in tgts])
-    res = (_lib.Result * max(1, nv * n))()
-    rep = (_lib.Report * max(1, nv * n))()
+    n, args, _, _keep = _pair_args(pairs)
+    nv, var = _variant_array(variants)
+    res, rep = _outputs(nv * n)
     opts = _report_options(max_correspondence_distance)
-    rc = L.se3icp_register_sweep_report(device, n, sp, ns, tp, nt, _lib.method_id(method), nv,
-                                        _variant_array(variants) if nv else None, max_group, res, C.byref(opts), rep)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_sweep_report")
+    _registered(_lib.load().se3icp_register_sweep_report(device, n, *args, _lib.method_id(method), nv, var, max_group,
+                                                         res, C.byref(opts), rep), "register_sweep_report")
     return _sweep_results(res, nv, n), _sweep_reports(rep, nv, n)
 
 
 def register_sweep_report_device(src_ptr: int, src_off, tgt_ptr: int, tgt_off, method: str, variants, device: int = 0,
                                  stream: int = 0, max_group: int = 0, max_correspondence_distance: float = 0.0):
     """register_sweep_report for clouds already in HBM."""
-    L = _lib.load()
-    n, nv = len(src_off) - 1, len(variants)
-    so = (C.c_int64 * (n + 1))(*[int(x) for x in src_off])
-    to = (C.c_int64 * (n + 1))(*[int(x) for x in tgt_off])
-    res = (_lib.Result * max(1, nv * n))()
-    rep = (_lib.Report * max(1, nv * n))()
+    n, args = _offset_args(src_ptr, src_off, tgt_ptr, tgt_off)
+    nv, var = _variant_array(variants)
+    res, rep = _outputs(nv * n)
     opts = _report_options(max_correspondence_distance)
-    rc = L.se3icp_register_sweep_report_device(device, n, C.c_void_p(src_ptr), so, C.c_void_p(tgt_ptr), to,
-                                               _lib.method_id(method), nv, _variant_array(variants) if nv else None,
-                                               max_group, res, C.c_void_p(stream) if stream else None,
-                                               C.byref(opts), rep)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_sweep_report_device")
+    _registered(_lib.load().se3icp_register_sweep_report_device(device, n, *args, _lib.method_id(method), nv, var,
+                                                                max_group, res, _stream_arg(stream), C.byref(opts),
+                                                                rep), "register_sweep_report_device")
     return _sweep_results(res, nv, n), _sweep_reports(rep, nv, n)
 
 
@@ -676,18 +664,11 @@ def register_graph(clouds, edges, method: str, params: _lib.Params | None = None
     register_batch's for that pair, but every distinct cloud is uploaded and ingested once and
     set up once per normalization it takes part in (se3icp_register_graph).  sharing: 0 the
     engine's choice, 1 .. 3 see include/se3icp.h."""
-    L = _lib.load()
-    cl = [_as_xyz(c) for c in clouds]
-    nc = len(cl)
-    dp = C.POINTER(C.c_double)
-    cp = (dp * max(nc, 1))(*[a.ctypes.data_as(dp) for a in cl])
-    cn = (C.c_int64 * max(nc, 1))(*[a.shape[0] for a in cl])
+    _keep, cargs = _cloud_args(clouds)
     n, es, et = _edge_arrays(edges)
-    res = (_lib.Result * max(n, 1))()
-    rc = L.se3icp_register_graph(device, nc, cp, cn, n, es, et, _lib.method_id(method),
-                                 C.byref(params or _lib.default_params()), int(sharing), res)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_graph")
+    res, _ = _outputs(n)
+    _registered(_lib.load().se3icp_register_graph(device, *cargs, n, es, et, _lib.method_id(method), _params_ref(params),
+                                                  int(sharing), res), "register_graph")
     return _results(res, n)
 
 
@@ -701,65 +682,36 @@ def register_graph_device(xyz_ptr: int, off, edges, method: str, params: _lib.Pa
                           device: int = 0, stream: int = 0, sharing: int = 0) -> list[PairResult]:
     """register_graph for clouds already in HBM: xyz_ptr is the device address of the
     concatenated AoS float64 xyz of every cloud, off the n_clouds+1 point offsets."""
-    L = _lib.load()
     nc = len(off) - 1
     co = (C.c_int64 * (nc + 1))(*[int(x) for x in off])
     n, es, et = _edge_arrays(edges)
-    res = (_lib.Result * max(n, 1))()
-    rc = L.se3icp_register_graph_device(device, nc, C.c_void_p(xyz_ptr), co, n, es, et, _lib.method_id(method),
-                                        C.byref(params or _lib.default_params()), int(sharing), res,
-                                        C.c_void_p(stream) if stream else None)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_graph_device")
+    res, _ = _outputs(n)
+    _registered(_lib.load().se3icp_register_graph_device(device, nc, C.c_void_p(xyz_ptr), co, n, es, et,
+                                                         _lib.method_id(method), _params_ref(params), int(sharing),
+                                                         res, _stream_arg(stream)), "register_graph_device")
     return _results(res, n)
 
 
 def register_graph_report(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
                           sharing: int = 0, max_correspondence_distance: float = 0.0, per_point: bool = False):
     """register_graph plus a PairReport per edge, as register_batch_report: (results, reports)."""
-    L = _lib.load()
-    cl = [_as_xyz(c) for c in clouds]
-    nc = len(cl)
-    dp = C.POINTER(C.c_double)
-    cp = (dp * max(nc, 1))(*[a.ctypes.data_as(dp) for a in cl])
-    cn = (C.c_int64 * max(nc, 1))(*[a.shape[0] for a in cl])
+    cl, cargs = _cloud_args(clouds)
     n, es, et = _edge_arrays(edges)
     counts = [cl[int(s)].shape[0] for s, _ in edges]
-    res = (_lib.Result * max(n, 1))()
-    rep = (_lib.Report * max(n, 1))()
-    idx = np.full(sum(counts), -1, np.int32) if per_point else None
-    dist = np.zeros(sum(counts)) if per_point else None
-    opts = _report_options(max_correspondence_distance, idx.ctypes.data if per_point else None,
-                           dist.ctypes.data if per_point else None)
-    rc = L.se3icp_register_graph_report(device, nc, cp, cn, n, es, et, _lib.method_id(method),
-                                        C.byref(params or _lib.default_params()), int(sharing), res, C.byref(opts), rep)
-    if rc not in (_lib.OK, _lib.ERR_NONFINITE):
-        raise _lib.Se3IcpError(rc, "register_graph_report")
-    ii = _split(idx, counts) if per_point else [None] * n
-    dd = _split(dist, counts) if per_point else [None] * n
-    return _results(res, n), [_report(rep[i], ii[i], dd[i]) for i in range(n)]
+    res, rep = _outputs(n)
+    opts, idx, dist = _per_point_options(max_correspondence_distance, counts, per_point)
+    _registered(_lib.load().se3icp_register_graph_report(device, *cargs, n, es, et, _lib.method_id(method),
+                                                         _params_ref(params), int(sharing), res, C.byref(opts), rep),
+                "register_graph_report")
+    return _results(res, n), _pair_reports(rep, counts, idx, dist)
 
 
 def register_graph_traced(clouds, edges, method: str, params: _lib.Params | None = None, edge: int = 0,
                           max_iters: int = 160, device: int = 0, sharing: int = 0):
     """register_graph with the per-iteration record of one edge (see register_batch_traced)."""
-    L = _lib.load()
-    ns = _as_xyz(clouds[int(edges[edge][0])]).shape[0]
-    tr = {"corr_idx": np.full((max_iters, ns), -1, np.int32), "corr_dist": np.zeros((max_iters, ns), np.float32),
-          "trim_key": np.zeros(max_iters, np.uint64), "T": np.zeros((max_iters, 4, 4)), "mse": np.zeros(max_iters),
-          "phase": np.zeros(max_iters, np.int32)}
-    t = _lib.Trace(edge, max_iters, tr["corr_idx"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   tr["corr_dist"].ctypes.data_as(C.POINTER(C.c_float)),
-                   tr["trim_key"].ctypes.data_as(C.POINTER(C.c_uint64)), tr["T"].ctypes.data_as(C.POINTER(C.c_double)),
-                   tr["mse"].ctypes.data_as(C.POINTER(C.c_double)), tr["phase"].ctypes.data_as(C.POINTER(C.c_int32)),
-                   0, 0)
-    _lib.check(L.se3icp_set_trace(device, C.byref(t)), "set_trace")
-    try:
+    with _armed_trace(device, edge, _as_xyz(clouds[int(edges[edge][0])]).shape[0], max_iters) as trace:
         res = register_graph(clouds, edges, method, params, device, sharing)
-    finally:
-        L.se3icp_set_trace(device, None)
-    n = int(t.iters_recorded)
-    return res, {k: v[:n] for k, v in tr.items()}
+    return res, trace
 
 
 def last_graph_stats(device: int = 0) -> dict:

@@ -305,3 +305,46 @@ def test_then_a_plain_batch_and_a_sweep(se3icp_mod, bunny_clouds):
     s1 = se3icp_mod.register_sweep(pairs, "se3_gicp", variants)
     assert [_bytes(r) for r in b0] == [_bytes(r) for r in b1]
     assert [[_bytes(r) for r in row] for row in s0] == [[_bytes(r) for r in row] for row in s1]
+
+
+def test_interleaved_entries_on_one_engine(se3icp_mod, bunny_clouds):
+    """The registration entries and the stage entries share one engine's geometry members and
+    buffers: a fixed sequence of all of them on engine slot 0 returns, call for call, what the
+    same call returns on an engine slot of its own."""
+    mod = se3icp_mod
+    pairs = [(bunny_clouds[0], bunny_clouds[1]), (bunny_clouds[2], bunny_clouds[3])]
+    params = mod.default_params(number_of_nn_for_LRF=60)
+    variants = mod.sweep_params(params, alpha_rot=[0.3, 3.0])
+    edges = [(1, 0), (2, 1), (3, 2)]
+    rng = np.random.default_rng(11)
+    q12, d12 = rng.standard_normal((200, 12)), rng.standard_normal((300, 12))
+    pts = bunny_clouds[0][:500]
+    calls = [
+        ("register_batch", lambda d: mod.register_batch(pairs, "se3_gicp", params, device=d)),
+        ("nearest_neighbors", lambda d: mod.nearest_neighbors(q12, d12, device=d)),
+        ("register_graph", lambda d: mod.register_graph(bunny_clouds, edges, "se3_gicp", params, device=d)),
+        ("knn_self", lambda d: mod.knn_self(pts, 8, device=d)),
+        ("register_sweep", lambda d: mod.register_sweep(pairs, "se3_gicp", variants, device=d)),
+        ("toldi_frames", lambda d: mod.toldi_frames(pts, 30, device=d)),
+        ("register_batch_report", lambda d: mod.register_batch_report(pairs, "se3_gicp", params, device=d,
+                                                                      max_correspondence_distance=0.05, per_point=True)),
+        ("estimate_normals", lambda d: mod.estimate_normals(pts, device=d)),
+        ("register_batch", lambda d: mod.register_batch(pairs, "se3_gicp", params, device=d)),
+    ]
+
+    def flat(x):  # every value a call returns, as comparable bytes
+        if isinstance(x, (list, tuple)):
+            return [flat(y) for y in x]
+        if isinstance(x, mod.PairResult):
+            return _bytes(x)
+        if isinstance(x, mod.PairReport):
+            f64 = np.array([x.fitness, x.inlier_rmse, x.final_mse, x.final_mse_change])
+            return (f64.tobytes(), x.information.tobytes(), x.n_inliers, x.switched, x.stop_reason,
+                    x.corr_idx.tobytes(), x.corr_dist.tobytes())
+        return (x.dtype.str, x.shape, x.tobytes()) if isinstance(x, np.ndarray) else x
+
+    together = [flat(f(0)) for _, f in calls]
+    for k, (name, f) in enumerate(calls):
+        alone = flat(f((k + 1) << 8))
+        assert together[k] == alone, f"call {k} ({name}) differs from its own-slot twin"
+    assert together[0] == together[-1]  # (the same batch before and after everything else)

@@ -94,6 +94,77 @@ def test_argument_checks_come_before_the_device(mod, entry):
         assert c.run(entry, method=m) == _lib.ERR_NO_DEVICE
 
 
+def _plain_call(mod, entry, n_pairs=1, null=None, n_src=50, n_tgt=60, method=5, k_lrf=30):
+    """One valid call of a non-report entry with single knobs turned; returns the status.
+    null: the name of one pointer argument passed as NULL ("src0" / "tgt0": the first pair's
+    cloud in a host entry's pointer array)."""
+    from se3icp import _lib
+    L = _lib.load()
+    dp = C.POINTER(C.c_double)
+    c = _Call(mod)
+    res = (_lib.Result * 2)()
+    prm = mod.default_params(number_of_nn_for_LRF=k_lrf)
+    var = (_lib.Params * 2)(mod.default_params(number_of_nn_for_LRF=k_lrf, alpha_rot=1.0), prm)
+    if entry in ("batch", "sweep"):
+        a = {"src": (dp * 1)(None if null == "src0" else c.src.ctypes.data_as(dp)), "n_src": (C.c_int64 * 1)(n_src),
+             "tgt": (dp * 1)(None if null == "tgt0" else c.tgt.ctypes.data_as(dp)), "n_tgt": (C.c_int64 * 1)(n_tgt)}
+    else:
+        a = {"src": C.c_void_p(4096), "n_src": (C.c_int64 * 2)(0, n_src),  # never dereferenced: no device is reached
+             "tgt": C.c_void_p(4096), "n_tgt": (C.c_int64 * 2)(0, n_tgt)}
+    a.update(params=C.byref(prm), variants=var, results=res)
+    if null in a:
+        a[null] = None
+    if entry == "batch":
+        return L.se3icp_register_batch(NO_SUCH_DEVICE, n_pairs, a["src"], a["n_src"], a["tgt"], a["n_tgt"], method,
+                                       a["params"], a["results"])
+    if entry == "batch_device":
+        return L.se3icp_register_batch_device(NO_SUCH_DEVICE, n_pairs, a["src"], a["n_src"], a["tgt"], a["n_tgt"],
+                                              method, a["params"], a["results"], None)
+    if entry == "sweep":
+        return L.se3icp_register_sweep(NO_SUCH_DEVICE, n_pairs, a["src"], a["n_src"], a["tgt"], a["n_tgt"], method, 2,
+                                       a["variants"], 0, a["results"])
+    return L.se3icp_register_sweep_device(NO_SUCH_DEVICE, n_pairs, a["src"], a["n_src"], a["tgt"], a["n_tgt"], method,
+                                          2, a["variants"], 0, a["results"], None)
+
+
+# (knobs of _plain_call, the status of the two sweep entries); the plain batch entries look the
+# device up before anything else and answer every row with ERR_NO_DEVICE
+_PLAIN_ROWS = [
+    (dict(), "NO_DEVICE"),
+    (dict(n_pairs=0), "INVALID_ARG"),
+    (dict(n_pairs=-1), "INVALID_ARG"),
+    (dict(null="src"), "INVALID_ARG"),
+    (dict(null="n_src"), "INVALID_ARG"),
+    (dict(null="tgt"), "INVALID_ARG"),
+    (dict(null="n_tgt"), "INVALID_ARG"),
+    (dict(null="results"), "INVALID_ARG"),
+    (dict(null="variants"), "INVALID_ARG"),  # (a batch's params: NULL means the defaults)
+    (dict(n_src=0), "EMPTY_CLOUD"),
+    (dict(n_tgt=0), "EMPTY_CLOUD"),
+    (dict(method=-1), "INVALID_METHOD"),
+    (dict(method=10), "INVALID_METHOD"),
+    (dict(method=5, k_lrf=0), "INVALID_ARG"),
+    (dict(method=2, k_lrf=0), "NO_DEVICE"),
+]
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_status_table_of_the_plain_entries(mod, entry):
+    """The status of every bad call of the four entries without a report, on a device ordinal
+    no machine has: the sweeps check their arguments first, se3icp_register_batch and
+    se3icp_register_batch_device look the device up first and leave the checks to the engine."""
+    from se3icp import _lib
+    rows = list(_PLAIN_ROWS)
+    if entry in ("batch", "sweep"):
+        rows += [(dict(null="src0"), "INVALID_ARG"), (dict(null="tgt0"), "INVALID_ARG")]
+    for knobs, want in rows:
+        if entry.startswith("batch"):
+            want = "NO_DEVICE"
+            if knobs.get("null") == "variants":
+                knobs = dict(null="params")
+        assert _plain_call(mod, entry, **knobs) == getattr(_lib, "ERR_" + want), (entry, knobs)
+
+
 def test_python_entries_fail_loudly_without_a_device(mod):
     from se3icp import _lib
     a = np.random.default_rng(1).random((40, 3))

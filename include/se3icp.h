@@ -254,6 +254,30 @@ int se3icp_register_graph_report_device(int device, int32_t n_clouds, const doub
 #define SE3ICP_GRAPH_STATS_N 9
 int se3icp_last_graph_stats(int device, int64_t* out, int n);
 
+/* The device batch entries (se3icp_register_batch_device, _report_device) cannot be told that
+ * two of their 2 * n_pairs cloud slots hold the same scan -- a chain of scans expanded into
+ * pairs holds every interior scan twice -- so they look.  Slots of equal point count are
+ * hashed on the device over their raw xyz bytes (64 bits, keyed with the count); slots of equal
+ * (count, hash) are compared byte for byte on the device against the first of them, and only
+ * a confirmed slot shares: never a hash match alone, a pointer or a batch position (-0.0 is
+ * not +0.0 here, and a NaN is itself).  With a confirmed duplicate the neighbour selection
+ * runs once per (cloud, normalization) class as in se3icp_register_graph at sharing 2, on the
+ * slots as they lie (nothing is uploaded or moved); without one the call is the plain batch
+ * plus the hash pass, and without two slots of one point count nothing is hashed at all.
+ * results[p] is bitwise what the plain batch returns.  A call that looks waits twice for the
+ * device during the setup (the hashes, with the normalization parameters the classes are
+ * planned from; the compare flags, only when some hash agreed) where the plain batch waits
+ * not at all (run_se3_*) or once.
+ * level: 0 the highest level that is built (= 2, the default of every engine), 1 off (the
+ * plain batch), 2 one selection per class.  Anything else is SE3ICP_ERR_INVALID_ARG, checked
+ * before the device is looked up.  The setting is the engine's (device | slot << 8) and holds
+ * until it is set again.  Neighbour-set adoption between the classes of one cloud is not
+ * built here either.  The host-pointer entries and the sweeps do not look: a caller with host
+ * buffers has se3icp_register_graph, which also uploads every cloud once.
+ * se3icp_last_graph_stats after a device batch at level 0 or 2: {distinct clouds, slots,
+ * classes, classes that selected, 0, 0, 0, 0, 0}. */
+int se3icp_set_batch_sharing(int device, int level);
+
 /* ------------------------------------------------------------- registration reports
  * What says whether a pose is any good, evaluated at the FINAL pose as Open3D's
  * RegistrationResult and GetInformationMatrixFromPointClouds are.  For every source point i

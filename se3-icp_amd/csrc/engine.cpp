@@ -158,6 +158,7 @@ hipError_t spin_phases(const volatile int32_t* slot, int n, hipStream_t s) {
 }
 
 static_assert(GS_COUNT == 9, "Engine::graph_stats_");
+constexpr size_t kShareMaxSlots = 65535;  // k_share_hash takes one grid row per slot
 constexpr int kStatSlots = 64;  // work counters: [64][kStatCols] u64 (spread against atomic contention)
 
 }  // namespace
@@ -635,9 +636,168 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
         for (int side = 0; side < 2; ++side)
             clouds[2 * p + side] = CloudReq{side == 0 ? src[p] : tgt[p], side == 0 ? ns[p] : nt[p],
                                             cloud_setup(mp, side, prm.alpha_rot, prm.beta_transl, true)};
-    rc = setup_clouds(clouds, on_device, true, mp.se3, prm.scale_preprocessing, call.s);
+    // resident clouds: slots that hold the same cloud share its setup (setup_pairs_shared).
+    // Slots of one point count are the only candidates; without two of them nothing is hashed.
+    bool look = false;
+    if (on_device && batch_sharing_ != 1) {
+        std::vector<int64_t> n(clouds.size());
+        for (size_t u = 0; u < clouds.size(); ++u) n[u] = clouds[u].n;
+        look = clouds.size() <= kShareMaxSlots && share_any_equal_n((int32_t)n.size(), n.data());
+        for (int64_t& g : graph_stats_) g = 0;
+        graph_stats_[GS_CLOUDS] = graph_stats_[GS_USES] = graph_stats_[GS_CLASSES] = (int64_t)clouds.size();
+        for (const CloudReq& c : clouds) graph_stats_[GS_FULL] += c.st.k_knn > 0;
+    }
+    rc = look ? setup_pairs_shared(clouds, mp, prm.scale_preprocessing, call.s)
+              : setup_clouds(clouds, on_device, true, mp.se3, prm.scale_preprocessing, call.s);
     if (rc) return rc;
     return run_pairs(mp, npairs, ns, nt, &prm, npairs, false, call, out, ropts, reports);
+}
+
+// ----------------------------------------------------------------------------- shared slots of a device batch
+// setup_clouds(clouds, on_device, pairs, normalize) for slots that may hold one cloud several
+// times (engine.hpp).  Every kernel setup_clouds queues is queued here, in its order and on its
+// tables, so a call without a confirmed duplicate is that path plus k_share_hash; the host
+// waits for the hashes while the device normalizes and builds the 3-D trees.
+int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const MethodPlan& mp, double scale_pre,
+                               hipStream_t s) {
+    const int U = (int)clouds.size();
+    const bool se3 = mp.se3;
+    int rc = upload_clouds(clouds, true, s);
+    if (rc) return rc;
+    const int nch = (int)h_chunks_.size();
+    if (!ensure<uint64_t>(d_share_hash_, U) || !ensure<SharePair>(d_share_pairs_, U) ||
+        !ensure<int32_t>(d_share_same_, U) || h_share_hash_.reserve(U) || h_share_same_.reserve(U) ||
+        h_share_setup_.reserve(U))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    View v = view();
+    HIPCHK(hipMemsetAsync(d_share_hash_.p, 0, sizeof(uint64_t) * U, s));
+    launch_share_hash(v, (unsigned long long*)d_share_hash_.p, s);
+    HIPCHK(hipMemcpyAsync(h_share_hash_, d_share_hash_.p, sizeof(uint64_t) * U, hipMemcpyDeviceToHost, s));
+    launch_ingest(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
+    HIPCHK(hipGetLastError());
+    if (se3) {
+        // (the device forms the normalization parameters, as in setup_clouds; its table comes
+        // back with the hashes: a class is the bits the device normalizes a slot with)
+        if (!ensure<double>(d_scales_, std::max(1, nclouds_ / 2))) return SE3ICP_ERR_OUT_OF_MEMORY;
+        launch_pair_centers(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_partial_.p, (double*)d_centers_.p,
+                            s);
+        launch_radius(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_centers_.p, (double*)d_partial_.p, s);
+        launch_pair_scales(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_partial_.p,
+                           (const double*)d_centers_.p, scale_pre, (double*)d_scales_.p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_share_setup_, d_setup_.p, sizeof(CloudSetup) * U, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(ev_[10], s));
+        for (int c = 0; c < nclouds_; ++c)
+            for (int a = 0; a < 3; ++a) h_setup_[c].f32_center[a] = 0.0;
+    } else {
+        std::vector<double> cen;
+        rc = host_centroids(s, &cen);  // (the hashes arrive with this wait)
+        if (rc) return rc;
+        for (int c = 0; c < nclouds_; ++c) {
+            for (int a = 0; a < 3; ++a) {
+                h_setup_[c].norm_center[a] = 0.0;
+                h_setup_[c].f32_center[a] = cen[3 * (c | 1) + a];
+            }
+            h_setup_[c].norm_scale = 1.0;
+        }
+        HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * nclouds_, hipMemcpyHostToDevice, s));
+    }
+    launch_normalize(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
+    HIPCHK(hipGetLastError());
+    rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+    if (rc) return rc;
+    if (se3) HIPCHK(spin_wait(ev_[10]));
+
+    // ---- candidates by (n, hash), confirmed byte for byte
+    std::vector<int64_t> n(U);
+    for (int u = 0; u < U; ++u) n[u] = clouds[u].n;
+    std::vector<int32_t> first, cloud;
+    const int ncand = share_candidates(U, n.data(), h_share_hash_, &first);
+    int nc = U;
+    if (ncand > 0) {
+        share_pairs_.clear();
+        for (int u = 0; u < U; ++u)
+            if (first[u] != u) share_pairs_.push_back(SharePair{u, first[u]});
+        HIPCHK(hipMemcpyAsync(d_share_pairs_.p, share_pairs_.data(), sizeof(SharePair) * ncand, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(d_share_same_.p, 1, sizeof(int32_t) * U, s));
+        launch_share_compare(v, (const SharePair*)d_share_pairs_.p, ncand, (int32_t*)d_share_same_.p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_share_same_, d_share_same_.p, sizeof(int32_t) * U, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipEventRecord(ev_[11], s));
+        HIPCHK(spin_wait(ev_[11]));
+        nc = share_clouds(U, first.data(), h_share_same_, &cloud);
+    }
+    if (nc == U) return setup_knn(s);  // every slot a cloud of its own: the batch's path
+
+    // ---- classes: a cloud under the bits the device normalizes the slot with
+    const CloudSetup* dev_table = se3 ? (const CloudSetup*)h_share_setup_ : h_setup_.data();
+    share_setup_.assign(dev_table, dev_table + U);
+    std::vector<GraphUse> use(U);
+    for (int u = 0; u < U; ++u) {
+        const CloudSetup& st = share_setup_[u];
+        use[u].cloud = cloud[u];
+        use[u].k_nrm = st.k_nrm;
+        use[u].norm_scale = st.norm_scale;
+        for (int a = 0; a < 3; ++a) {
+            use[u].norm_center[a] = st.norm_center[a];
+            use[u].f32_center[a] = st.f32_center[a];
+        }
+    }
+    GraphPlan plan;
+    graph_plan_uses(U, use.data(), se3, true, &plan);
+    graph_stats_[GS_CLOUDS] = nc;
+    graph_stats_[GS_CLASSES] = (int64_t)plan.classes.size();
+    return select_by_class(plan, share_setup_, mp, s);
+}
+
+// The neighbour selection of planned uses (engine.hpp).  The tables the copies below read stay
+// alive in the engine until the call's last synchronisation.
+int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>& batch, const MethodPlan& mp,
+                            hipStream_t s) {
+    const int U = (int)batch.size(), K = (int)plan.classes.size();
+    const bool se3 = mp.se3;
+    std::vector<int32_t> home(K, -1);  // first use of each class
+    for (int u = 0; u < U; ++u)
+        if (home[plan.use_class[u]] < 0) home[plan.use_class[u]] = u;
+    sel_batch_ = batch;
+    sel_run_ = sel_batch_;
+    sel_chunks_.clear();
+    sel_seg_.assign(U, GraphSeg{});
+    graph_stats_[GS_FULL] = 0;
+    for (int u = 0; u < U; ++u) {
+        const int k = plan.use_class[u];
+        const GraphClass& gc = plan.classes[k];
+        // the setup's table: a home use selects for its class (the largest normals k of the
+        // class's uses; none where another class of the cloud owns the normals), the others
+        // select nothing
+        CloudSetup& st = sel_run_[u];
+        const bool is_home = home[k] == u;
+        st.k_lrf = is_home ? mp.k_lrf : 0;
+        st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
+        st.k_knn = std::max(st.k_lrf, st.k_nrm);
+        graph_stats_[GS_FULL] += st.k_knn > 0;
+        const int hf = home[k], hn = home[gc.nrm_from];  // where its frames / normals are computed
+        sel_seg_[u] = GraphSeg{h_clouds_[hf].off, hf, h_clouds_[hn].off, (hf != u && se3) ? 1 : 0};
+        if ((hf != u && se3) || hn != u)
+            for (int64_t p0 = 0; p0 < h_clouds_[u].n; p0 += kChunk) sel_chunks_.push_back(ChunkWork{u, (int32_t)p0});
+    }
+    const int nchS = (int)sel_chunks_.size();
+    if (!ensure<ChunkWork>(g_chunks_, nchS) || !ensure<GraphSeg>(g_seg_, U)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    h_setup_ = sel_run_;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_run_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
+    const int rc = setup_knn(s);
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    // the batch's own table from here on (the copies below read cf_target of the use itself)
+    h_setup_ = sel_batch_;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_batch_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
+    if (nchS > 0) {
+        HIPCHK(hipMemcpyAsync(g_chunks_.p, sel_chunks_.data(), sizeof(ChunkWork) * nchS, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g_seg_.p, sel_seg_.data(), sizeof(GraphSeg) * U, hipMemcpyHostToDevice, s));
+        launch_graph_share(view(), (const ChunkWork*)g_chunks_.p, nchS, (const GraphSeg*)g_seg_.p, s);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
 }
 
 // Work table of k_reduce and the per-pair buffers of a batch (see engine.hpp).
@@ -1332,13 +1492,10 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
     nclouds_ = 2 * P;
     npairs_ = P;
     ntot_ = NU;
-    std::vector<int32_t> home(K, -1);  // first use of each class
-    for (int u = 0; u < 2 * P; ++u)
-        if (home[plan.use_class[u]] < 0) home[plan.use_class[u]] = u;
     std::vector<CloudDev> clU(2 * (size_t)P);
-    std::vector<CloudSetup> stU(2 * (size_t)P), stRun(2 * (size_t)P);  // a batch's table / the setup's
-    std::vector<ChunkWork> chU, chShare;
-    std::vector<GraphSeg> segU(2 * (size_t)P), segShare(2 * (size_t)P);
+    std::vector<CloudSetup> stU(2 * (size_t)P);  // a batch's table
+    std::vector<ChunkWork> chU;
+    std::vector<GraphSeg> segU(2 * (size_t)P);
     std::vector<double> cenU(6 * (size_t)P), scaleU(P, 1.0);
     int max_n = 1;
     {
@@ -1361,32 +1518,13 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
             max_n = std::max<int>(max_n, (int)n);
             off += n;
         }
-        for (int u = 0; u < 2 * P; ++u) {
-            const int k = plan.use_class[u];
-            const GraphClass& gc = plan.classes[k];
-            // the setup's table: a home use selects for its class (the largest normals k of the
-            // class's uses; none where another class of the cloud owns the normals), the others
-            // select nothing
-            CloudSetup& st = stRun[u];
-            st = stU[u];
-            const bool is_home = home[k] == u;
-            st.k_lrf = is_home ? mp.k_lrf : 0;
-            st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
-            st.k_knn = std::max(st.k_lrf, st.k_nrm);
-            graph_stats_[GS_FULL] += st.k_knn > 0;
-            const int hf = home[k], hn = home[gc.nrm_from];  // where its frames / normals are computed
-            segShare[u] = GraphSeg{clU[hf].off, hf, clU[hn].off, (hf != u && se3) ? 1 : 0};
-            if ((hf != u && se3) || hn != u)
-                for (int64_t p0 = 0; p0 < clU[u].n; p0 += kChunk) chShare.push_back(ChunkWork{u, (int32_t)p0});
-        }
     }
     tree_L_ = tree_depth_for(max_n);
     h_clouds_ = clU;
-    h_setup_ = stRun;
-    const int nchU2 = (int)chU.size(), nchS = (int)chShare.size();
-    if (!ensure<ChunkWork>(g_chunks_, nchS)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    h_setup_ = stU;
+    const int nchU2 = (int)chU.size();
     HIPCHK(hipMemcpyAsync(d_clouds_.p, clU.data(), sizeof(CloudDev) * 2 * P, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_setup_.p, stRun.data(), sizeof(CloudSetup) * 2 * P, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_setup_.p, stU.data(), sizeof(CloudSetup) * 2 * P, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_chunks_.p, chU.data(), sizeof(ChunkWork) * nchU2, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(g_seg_.p, segU.data(), sizeof(GraphSeg) * 2 * P, hipMemcpyHostToDevice, s));
     if (se3) {
@@ -1398,18 +1536,8 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
     HIPCHK(hipGetLastError());
     rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
     if (rc) return rc;
-    rc = setup_knn(s);
+    rc = select_by_class(plan, stU, mp, s);
     if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    // the batch's own table from here on (the copies below read cf_target of the use itself)
-    h_setup_ = stU;
-    HIPCHK(hipMemcpyAsync(d_setup_.p, stU.data(), sizeof(CloudSetup) * 2 * P, hipMemcpyHostToDevice, s));
-    if (nchS > 0) {
-        HIPCHK(hipMemcpyAsync(g_chunks_.p, chShare.data(), sizeof(ChunkWork) * nchS, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g_seg_.p, segShare.data(), sizeof(GraphSeg) * 2 * P, hipMemcpyHostToDevice, s));
-        launch_graph_share(view(), (const ChunkWork*)g_chunks_.p, nchS, (const GraphSeg*)g_seg_.p, s);
-        HIPCHK(hipGetLastError());
-    }
     return run_pairs(mp, P, ns.data(), nt.data(), &prm, P, false, call, out, ropts, reports);
 }
 

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include <vector>
 
+#include "graph.hpp"
 #include "pairmath.hpp"
 #include "se3icp.h"
 #include "view.hpp"
@@ -86,6 +87,7 @@ class Engine {
     void set_trace(se3icp_trace* t) { trace_ = t; }
     void set_lrf_exact(int mode) { lrf_exact_only_ = mode; }
     void set_nn_events(bool on) { nn_events_ = on; }
+    void set_batch_sharing(int level) { batch_sharing_ = level; }
     const KernelTimes& kernel_times() const { return ktimes_; }
 
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
@@ -107,7 +109,9 @@ class Engine {
                        const int32_t* tgt, bool on_device, int method, const se3icp_params& prm, int sharing,
                        se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts = nullptr,
                        se3icp_report* reports = nullptr);
-    const int64_t* graph_stats() const { return graph_stats_; }  // [GS_COUNT] of the last register_graph
+    // [GS_COUNT] of the last register_graph, or of the last device batch that looked for shared
+    // clouds (setup_pairs_shared)
+    const int64_t* graph_stats() const { return graph_stats_; }
 
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
@@ -160,6 +164,20 @@ class Engine {
                      hipStream_t s);
     // kNN / frames / normals of the clouds set up so far (step 4 of setup_clouds)
     int setup_knn(hipStream_t s);
+    // setup_clouds for the 2P resident cloud slots of a device batch that may hold one cloud
+    // several times (graph.hpp): the slots are ingested, normalized and given their 3-D trees
+    // in place exactly as setup_clouds does, hashed on the way, and compared where the hashes
+    // agree; with a confirmed duplicate the neighbour selection runs once per class
+    // (select_by_class), otherwise as setup_knn.  Two host waits where setup_clouds has none
+    // (run_se3_*) or one (vanilla): the hashes, with the normalization parameters the class
+    // plan needs; the compare flags, only when some hash agreed.
+    int setup_pairs_shared(const std::vector<CloudReq>& clouds, const MethodPlan& mp, double scale_pre, hipStream_t s);
+    // The neighbour selection of planned uses that are laid out, normalized and have their 3-D
+    // trees: the first use of every class selects for it (setup_knn over a table in which the
+    // other uses ask for nothing), k_graph_share hands its rows and normals to the others, and
+    // `batch`, the uses' own setup table, is the device's and the host's from there on.
+    int select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>& batch, const MethodPlan& mp,
+                        hipStream_t s);
     int setup_chunks(int npairs, hipStream_t s);
     // run_pairs: everything behind the clouds' setup, for npairs pairs laid out src 0, tgt 0,
     // src 1, ...: the 12-D kd-trees over the weighted SE(3) elements (SE(3) methods),
@@ -209,6 +227,8 @@ class Engine {
     // profiled batches (each marker leaves the GPU idle a few us;
     // time_se3_correspondence_search_ms is then 0)
     bool nn_events_ = true;
+    // se3icp_set_batch_sharing: 0 the highest level built (= 2), 1 off, 2 one selection per class
+    int batch_sharing_ = 0;
     se3icp_trace* trace_ = nullptr;      // armed per-iteration record of one pair (se3icp_set_trace)
     int record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t s);
     double trace_prev_[kStatCols] = {};
@@ -240,6 +260,19 @@ class Engine {
     // register_graph: the distinct clouds' raw columns and confidences (swapped with xyz64 /
     // conf64 between the call's two layouts), the segment and chunk tables of the k_graph kernels
     DevBuf g_raw_xyz_{bufs_}, g_raw_conf_{bufs_}, g_seg_{bufs_}, g_chunks_{bufs_};
+    // setup_pairs_shared: the slots' hashes, the compare table and its flags, their host copies
+    // and the host copy of the device's setup table
+    DevBuf d_share_hash_{bufs_}, d_share_pairs_{bufs_}, d_share_same_{bufs_};
+    Pinned<uint64_t> h_share_hash_{pins_};
+    Pinned<int32_t> h_share_same_{pins_};
+    Pinned<CloudSetup> h_share_setup_{pins_};
+    std::vector<SharePair> share_pairs_;
+    std::vector<CloudSetup> share_setup_;
+    // select_by_class: the uses' own setup table, the selection's, the chunks and segments of
+    // k_graph_share (host side of copies that run until the call's last synchronisation)
+    std::vector<CloudSetup> sel_batch_, sel_run_;
+    std::vector<ChunkWork> sel_chunks_;
+    std::vector<GraphSeg> sel_seg_;
     int64_t graph_stats_[9] = {};
     Pinned<PairDev> h_pairs_{pins_};
     Pinned<double> h_red_{pins_}, h_partial_{pins_};
@@ -257,7 +290,8 @@ class Engine {
     Pinned<unsigned long long> h_loop_stats_{pins_};  // loop NN work counters (pinned: an async copy, not a staged one)
     bool lrf_stats_pending_ = false;
     // 6/7: k_lrf time; 12/13/14: batch begin / setup done / loop done (GPU-timeline phase
-    // times); 8/9: a sweep's shared setup done / group begin; 15: sync_stream; the rest unused
+    // times); 8/9: a sweep's shared setup done / group begin; 10/11: setup_pairs_shared's hashes
+    // and compare flags on the host; 15: sync_stream; the rest unused
     hipEvent_t ev_[16];
     // loop iterations in flight: kernel-time events and launched NN phases per ring slot
     static constexpr int kLoopRing = 4, kLoopEv = 7;

@@ -11,6 +11,8 @@
 // (cloud, bits of norm_scale, bits of f32_center).  Uses of one class are bitwise the same
 // cloud to every setup kernel, so the class's neighbour selection, frames and normals -- the
 // bulk of the setup -- run once, at its first use, and are copied to the others.
+// The device batch entries find the slots that hold one cloud by content and plan the same
+// classes over them (share_candidates, share_clouds, graph_plan_uses below).
 // This header holds the plan, which needs no device.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +21,7 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <utility>
 #include <vector>
 
 namespace se3icp {
@@ -60,62 +63,66 @@ struct GraphPlan {
     std::vector<GraphClass> classes; // in order of first use
 };
 
-// Plan the classes of P edges.
-//   normalize: the run_se3_* preprocessing (centre on the own centroid, scale by the pair);
-//              otherwise raw coordinates with the f32 copy centred on the edge's target.
-//   center [3 * n_clouds], radius [n_clouds]: GetCenter and the largest |p - center| of every
-//              cloud an edge uses (radius is read only when normalize).
+// A use as the planner sees it: its cloud, the EstimateNormals k it asks for and the
+// normalization it runs under.
+struct GraphUse {
+    int32_t cloud;
+    int32_t k_nrm;
+    double norm_center[3];
+    double norm_scale;
+    double f32_center[3];
+};
+
+// Plan the classes of uses 0 .. n_uses - 1 (use 2p the source of pair p, 2p + 1 its target).
+// A class is (cloud, bits of norm_center, norm_scale and f32_center).
+//   normalize: the run_se3_* preprocessing; otherwise raw coordinates with only the f32 copy
+//              centred.
 //   dedupe:    false gives every use a class of its own (sharing level 1).
 // Without normalization the classes of a cloud differ only in the centre of their f32 copy:
 // the exact kNN and the normals are the same bits, so the cloud's first class with normals
 // computes them (nrm_from) and the others copy.
-inline void graph_plan(int32_t n_pairs, const int32_t* src, const int32_t* tgt, bool normalize, double scale_pre,
-                       const double* center, const double* radius, int k_nrm_src, int k_nrm_tgt, bool dedupe,
-                       GraphPlan* plan) {
+inline void graph_plan_uses(int32_t n_uses, const GraphUse* use, bool normalize, bool dedupe, GraphPlan* plan) {
     struct Key {
         int32_t cloud;
-        uint64_t b[4];
+        uint64_t b[7];
         bool operator<(const Key& o) const {
             if (cloud != o.cloud) return cloud < o.cloud;
             return std::memcmp(b, o.b, sizeof(b)) < 0;
         }
     };
     std::map<Key, int32_t> seen;
-    plan->use_class.assign(2 * (size_t)n_pairs, -1);
+    plan->use_class.assign((size_t)n_uses, -1);
     plan->classes.clear();
-    for (int32_t p = 0; p < n_pairs; ++p) {
-        const double scale = normalize ? graph_pair_scale(scale_pre, radius[src[p]], radius[tgt[p]]) : 1.0;
-        for (int side = 0; side < 2; ++side) {
-            const int32_t c = side == 0 ? src[p] : tgt[p];
-            GraphClass g{};
-            g.cloud = c;
-            g.k_nrm = side == 0 ? k_nrm_src : k_nrm_tgt;
-            g.n_uses = 1;
-            g.norm_scale = scale;
-            for (int a = 0; a < 3; ++a) {
-                g.norm_center[a] = normalize ? center[3 * c + a] : 0.0;
-                g.f32_center[a] = normalize ? 0.0 : center[3 * tgt[p] + a];
-            }
-            Key k{};
-            k.cloud = c;
-            std::memcpy(&k.b[0], &g.norm_scale, 8);
-            std::memcpy(&k.b[1], g.f32_center, 24);
-            int32_t id = -1;
-            if (dedupe) {
-                auto it = seen.find(k);
-                if (it != seen.end()) id = it->second;
-            }
-            if (id < 0) {
-                id = (int32_t)plan->classes.size();
-                plan->classes.push_back(g);
-                if (dedupe) seen[k] = id;
-            } else {
-                GraphClass& h = plan->classes[id];
-                h.k_nrm = h.k_nrm > g.k_nrm ? h.k_nrm : g.k_nrm;
-                h.n_uses++;
-            }
-            plan->use_class[2 * (size_t)p + side] = id;
+    for (int32_t u = 0; u < n_uses; ++u) {
+        GraphClass g{};
+        g.cloud = use[u].cloud;
+        g.k_nrm = use[u].k_nrm;
+        g.n_uses = 1;
+        g.norm_scale = use[u].norm_scale;
+        for (int a = 0; a < 3; ++a) {
+            g.norm_center[a] = use[u].norm_center[a];
+            g.f32_center[a] = use[u].f32_center[a];
         }
+        Key k{};
+        k.cloud = g.cloud;
+        std::memcpy(&k.b[0], &g.norm_scale, 8);
+        std::memcpy(&k.b[1], g.f32_center, 24);
+        std::memcpy(&k.b[4], g.norm_center, 24);
+        int32_t id = -1;
+        if (dedupe) {
+            auto it = seen.find(k);
+            if (it != seen.end()) id = it->second;
+        }
+        if (id < 0) {
+            id = (int32_t)plan->classes.size();
+            plan->classes.push_back(g);
+            if (dedupe) seen[k] = id;
+        } else {
+            GraphClass& h = plan->classes[id];
+            h.k_nrm = h.k_nrm > g.k_nrm ? h.k_nrm : g.k_nrm;
+            h.n_uses++;
+        }
+        plan->use_class[u] = id;
     }
     std::map<int32_t, int32_t> owner;  // cloud -> its first class with normals
     for (int32_t k = 0; k < (int32_t)plan->classes.size(); ++k) {
@@ -126,6 +133,81 @@ inline void graph_plan(int32_t n_pairs, const int32_t* src, const int32_t* tgt, 
         if (it == owner.end()) owner[g.cloud] = k;
         else if (plan->classes[it->second].k_nrm == g.k_nrm) g.nrm_from = it->second;
     }
+}
+
+// Plan the classes of P edges over clouds the caller names.
+//   normalize: centre on the own centroid, scale by the pair; otherwise the f32 copy is centred
+//              on the edge's target.
+//   center [3 * n_clouds], radius [n_clouds]: GetCenter and the largest |p - center| of every
+//              cloud an edge uses (radius is read only when normalize).
+inline void graph_plan(int32_t n_pairs, const int32_t* src, const int32_t* tgt, bool normalize, double scale_pre,
+                       const double* center, const double* radius, int k_nrm_src, int k_nrm_tgt, bool dedupe,
+                       GraphPlan* plan) {
+    std::vector<GraphUse> use(2 * (size_t)n_pairs);
+    for (int32_t p = 0; p < n_pairs; ++p) {
+        const double scale = normalize ? graph_pair_scale(scale_pre, radius[src[p]], radius[tgt[p]]) : 1.0;
+        for (int side = 0; side < 2; ++side) {
+            const int32_t c = side == 0 ? src[p] : tgt[p];
+            GraphUse& g = use[2 * (size_t)p + side];
+            g.cloud = c;
+            g.k_nrm = side == 0 ? k_nrm_src : k_nrm_tgt;
+            g.norm_scale = scale;
+            for (int a = 0; a < 3; ++a) {
+                g.norm_center[a] = normalize ? center[3 * c + a] : 0.0;
+                g.f32_center[a] = normalize ? 0.0 : center[3 * tgt[p] + a];
+            }
+        }
+    }
+    graph_plan_uses(2 * n_pairs, use.data(), normalize, dedupe, plan);
+}
+
+// ---- content-detected sharing of a device batch (Engine::setup_pairs_shared)
+// The device batch entries take 2P cloud slots and cannot be told that two of them hold the
+// same scan, so they look: every slot's raw xyz bytes are hashed on the device (k_share_hash,
+// 64 bits, keyed with the point count), slots of equal (n, hash) are candidates, and a
+// candidate shares only after a byte-for-byte device compare against the first slot of its
+// group (k_share_compare).  Never by pointer, never by batch position.
+// se3icp_set_batch_sharing
+constexpr int kBatchSharingMin = 0, kBatchSharingMax = 2;
+
+// Two slots of the same point count: without one there is nothing to hash.
+inline bool share_any_equal_n(int32_t n_slots, const int64_t* n) {
+    std::map<int64_t, int32_t> seen;
+    for (int32_t u = 0; u < n_slots; ++u)
+        if (++seen[n[u]] > 1) return true;
+    return false;
+}
+
+// first[u]: the first slot with u's (n, hash) -- u itself where none precedes it.  Returns the
+// number of slots with first[u] != u: the compares to run.
+inline int32_t share_candidates(int32_t n_slots, const int64_t* n, const uint64_t* hash, std::vector<int32_t>* first) {
+    std::map<std::pair<int64_t, uint64_t>, int32_t> seen;
+    first->assign((size_t)n_slots, -1);
+    int32_t cand = 0;
+    for (int32_t u = 0; u < n_slots; ++u) {
+        auto it = seen.find({n[u], hash[u]});
+        if (it == seen.end()) {
+            seen[{n[u], hash[u]}] = u;
+            (*first)[u] = u;
+        } else {
+            (*first)[u] = it->second;
+            ++cand;
+        }
+    }
+    return cand;
+}
+
+// cloud[u]: the distinct cloud slot u holds, numbered in order of first slot.  same[u] (read
+// where first[u] != u): nonzero iff the compare found u's bytes equal to first[u]'s.  A
+// hash-equal slot that the compare did not confirm is a cloud of its own -- also against a
+// later slot of its group, which was compared with the group's first slot only: a sharing
+// missed (after a 64-bit collision), never one made on the hash alone.  Returns the clouds.
+inline int32_t share_clouds(int32_t n_slots, const int32_t* first, const int32_t* same, std::vector<int32_t>* cloud) {
+    cloud->assign((size_t)n_slots, -1);
+    int32_t nc = 0;
+    for (int32_t u = 0; u < n_slots; ++u)
+        (*cloud)[u] = (first[u] != u && same[u]) ? (*cloud)[first[u]] : nc++;
+    return nc;
 }
 
 // Argument checks of the graph entries (before the device is looked up).  n_pts may be null
@@ -154,6 +236,12 @@ struct ChunkWork;
 // columns.  k_graph_share: src_off / src_cloud are the first slot and the cloud whose SE(3)
 // rows it takes (frames != 0), nrm_off the first slot of its normals (its own: none copied).
 struct GraphSeg { int32_t src_off; int32_t src_cloud; int32_t nrm_off; int32_t frames; };
+// k_share_compare: slot's bytes against those of the first slot of its group
+struct SharePair { int32_t slot; int32_t first; };
+// hash[u] += the content hash of cloud slot u's raw input (the caller clears it)
+void launch_share_hash(const View& v, unsigned long long* hash, hipStream_t s);
+// same[pair.slot] = 0 where the slot's bytes differ from pair.first's (the caller presets nonzero)
+void launch_share_compare(const View& v, const SharePair* pairs, int npairs, int32_t* same, hipStream_t s);
 // a use's normalized columns from the shared raw columns: the arithmetic of k_normalize
 void launch_graph_normalize(const View& v, const ChunkWork* chunks, int nchunks, const GraphSeg* seg,
                             const double* raw_xyz64, const double* raw_conf64, hipStream_t s);

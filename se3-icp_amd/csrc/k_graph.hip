@@ -13,6 +13,10 @@
 //                      frame kernels' epilogue (store_frame_rows): a cf target's translation
 //                      comes from its point, whichever side the computing use was on.
 // Raw columns and uses share the column stride (View::ld).  No atomics, no LDS.
+// And the two kernels by which a device batch finds the slots that hold one cloud (graph.hpp):
+//   k_share_hash       a 64-bit content hash of every slot's raw input (one integer atomic per
+//                      wavefront);
+//   k_share_compare    a slot's bytes against those of the first slot with its hash.
 #include <hip/hip_runtime.h>
 
 #include "devmath.hpp"
@@ -82,7 +86,60 @@ __global__ __launch_bounds__(kBlock) void k_graph_share(View v, const ChunkWork*
     }
 }
 
+// ---- content-detected sharing of a device batch (Engine::setup_pairs_shared)
+// A slot's hash is the sum modulo 2^64 of a mixed word per 8-byte word of its raw xyz, the mix
+// keyed with the word's index and the slot's point count: a sum, so the blocks of a slot
+// combine in any order to the same value (integer atomics; deterministic).
+constexpr int kShareBlocks = 32;  // blocks per slot, grid-strided over its words
+
+__device__ __forceinline__ unsigned long long share_mix(unsigned long long word, unsigned long long index,
+                                                        unsigned long long n) {
+    unsigned long long x = word + (index + 1) * 0x9E3779B97F4A7C15ull + n * 0xD6E8FEB86659FD93ull;
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+
+__global__ __launch_bounds__(kBlock) void k_share_hash(View v, unsigned long long* hash) {
+    const int u = blockIdx.y;
+    const unsigned long long n = (unsigned long long)v.clouds[u].n;
+    const unsigned long long* in = reinterpret_cast<const unsigned long long*>(v.in_ptr[u]);
+    const size_t words = 3 * (size_t)n;
+    unsigned long long sum = 0;
+    for (size_t w = (size_t)blockIdx.x * kBlock + threadIdx.x; w < words; w += (size_t)kShareBlocks * kBlock)
+        sum += share_mix(in[w], w, n);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if ((threadIdx.x & 63) == 0 && sum != 0) atomicAdd(hash + u, sum);
+}
+
+// same[pair.slot] = 0 where a word of the slot differs from the same word of pair.first (the
+// caller presets 1); both hold clouds[pair.slot].n points.  Bytes, not values: -0.0 differs from
+// +0.0 and a NaN equals itself.
+__global__ __launch_bounds__(kBlock) void k_share_compare(View v, const SharePair* pairs, int32_t* same) {
+    const SharePair pr = pairs[blockIdx.y];
+    const unsigned long long* a = reinterpret_cast<const unsigned long long*>(v.in_ptr[pr.slot]);
+    const unsigned long long* b = reinterpret_cast<const unsigned long long*>(v.in_ptr[pr.first]);
+    const size_t words = 3 * (size_t)v.clouds[pr.slot].n;
+    bool differ = false;
+    for (size_t w = (size_t)blockIdx.x * kBlock + threadIdx.x; w < words; w += (size_t)kShareBlocks * kBlock)
+        differ |= a[w] != b[w];
+    if (differ) same[pr.slot] = 0;
+}
+
 }  // namespace
+
+void launch_share_hash(const View& v, unsigned long long* hash, hipStream_t s) {
+    if (v.nclouds > 0) hipLaunchKernelGGL(k_share_hash, dim3(kShareBlocks, v.nclouds), dim3(kBlock), 0, s, v, hash);
+}
+
+void launch_share_compare(const View& v, const SharePair* pairs, int npairs, int32_t* same, hipStream_t s) {
+    if (npairs > 0)
+        hipLaunchKernelGGL(k_share_compare, dim3(kShareBlocks, npairs), dim3(kBlock), 0, s, v, pairs, same);
+}
 
 void launch_graph_normalize(const View& v, const ChunkWork* chunks, int nchunks, const GraphSeg* seg,
                             const double* raw_xyz64, const double* raw_conf64, hipStream_t s) {

@@ -16,7 +16,8 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            PairReport, register_batch_report, register_batch_report_device, register_sweep_report,
                            register_sweep_report_device,
                            expand_edges, last_graph_stats, register_graph, register_graph_device,
-                           register_graph_report, register_graph_traced, register_sequence, sequence_edges)
+                           register_graph_report, register_graph_traced, register_sequence, sequence_edges,
+                           set_batch_sharing)
 from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
@@ -28,4 +29,5 @@ __all__ = [
     "register_sweep_report", "register_sweep_report_device",
     "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
     "register_graph_report", "register_graph_traced", "last_graph_stats",
+    "set_batch_sharing",
 ]

@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_register_batch", "se3icp_register_batch_device", "se3icp_register",
     "se3icp_register_sweep", "se3icp_register_sweep_device",
     "se3icp_register_graph", "se3icp_register_graph_device", "se3icp_register_graph_report",
-    "se3icp_register_graph_report_device", "se3icp_last_graph_stats",
+    "se3icp_register_graph_report_device", "se3icp_last_graph_stats", "se3icp_set_batch_sharing",
     "se3icp_report_version", "se3icp_register_batch_report", "se3icp_register_batch_report_device",
     "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
     "se3icp_request_report", "se3icp_get_report",
@@ -224,6 +224,8 @@ def load():
     L.se3icp_set_trace.argtypes = [C.c_int, C.POINTER(Trace)]
     L.se3icp_set_lrf_exact.argtypes = [C.c_int, C.c_int]
     L.se3icp_set_nn_events.argtypes = [C.c_int, C.c_int]
+    # (se3icp_set_batch_sharing(int, int) is called with ctypes' default int conversion and
+    # resolved at its first call: SE3ICP_LIB may name an older build for an A/B run)
     _lib = L
     return L
 

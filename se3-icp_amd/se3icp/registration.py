@@ -715,10 +715,20 @@ def register_graph_traced(clouds, edges, method: str, params: _lib.Params | None
 
 
 def last_graph_stats(device: int = 0) -> dict:
-    """Counters of the last register_graph on `device` (se3icp_last_graph_stats)."""
+    """Counters of the last register_graph on `device`, or of its last device batch that looked
+    for shared clouds (se3icp_last_graph_stats, se3icp_set_batch_sharing)."""
     out = (C.c_int64 * len(_lib.GRAPH_STATS))()
     _lib.check(_lib.load().se3icp_last_graph_stats(device, out, len(_lib.GRAPH_STATS)), "last_graph_stats")
     return {k: int(out[i]) for i, k in enumerate(_lib.GRAPH_STATS)}
+
+
+def set_batch_sharing(level: int, device: int = 0) -> None:
+    """What the device batch entries (register_batch_device, register_batch_report_device,
+    DeviceBatchRunner) do about cloud slots that hold the same cloud, detected by content on the
+    device (se3icp_set_batch_sharing): 0 the highest level built (the default), 1 nothing (the
+    plain batch), 2 one neighbour selection per (cloud, normalization) class.  Results are
+    bitwise the same at every level; last_graph_stats() describes the last such call."""
+    _lib.check(_lib.load().se3icp_set_batch_sharing(int(device), int(level)), "set_batch_sharing")
 
 
 def toldi_frames(pts, k: int, device: int = 0) -> np.ndarray:

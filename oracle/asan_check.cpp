@@ -133,6 +133,15 @@ int main(int argc, char** argv) {
         CHECK(refcpu_estimate_normals(src.data(), n, k, nr.data()) == 0, "normals k=%d", k);
         CHECK(refcpu_gicp_covariances(nr.data(), n, 1e-3, cov.data()) == 0, "gicp covariances");
     }
+    {  // the eigen-solvers on their own: a generic, a diagonal and the zero matrix
+        const double a[18] = {2, 0.5, -0.25, 3, 0.125, 1, 4, 0, 0, 1, 0, 2, 0, 0, 0, 0, 0, 0};
+        double vj[9], vf[9];
+        CHECK(refcpu_sym_eig3_smallest(a, 3, vj) == 0, "sym_eig3_smallest");
+        CHECK(refcpu_fast_eigen3x3(a, 3, vf) == 0, "fast_eigen3x3");
+        CHECK(vj[3] == 0 && std::fabs(vj[4]) == 1 && vj[5] == 0, "jacobi on a diagonal matrix");
+        CHECK(vf[3] == 0 && vf[4] == 1 && vf[5] == 0, "FastEigen3x3 on a diagonal matrix");
+        CHECK(vf[6] == 0 && vf[7] == 0 && vf[8] == 0, "FastEigen3x3 on the zero matrix");
+    }
     {
         std::vector<int32_t> idx(n);
         std::vector<double> dd(n);

@@ -149,6 +149,17 @@ void sym_eig3(const Mat3& A, double w[3], Mat3& V) {
         for (int k = 0; k < 3; k++) V.m[k][c] = v[k][ord[c]];
     }
 }
+// The eigenvector of the smallest eigenvalue, at unit length (ISR.cpp:281).  Where the two
+// smallest eigenvalues coincide the sweeps above keep rotating rounding noise within their plane
+// up to the sweep limit, and the accumulated column drifts off unit length by about an eps per
+// rotation; Eigen's vectors are unit vectors.
+Vec3 sym_eig3_smallest(const Mat3& A) {
+    double w[3];
+    Mat3 V;
+    sym_eig3(A, w, V);
+    const Vec3 n(V.m[0][0], V.m[1][0], V.m[2][0]);
+    return (1.0 / std::sqrt(dot(n, n))) * n;
+}
 
 // ------------------------------------------------ [3P] Open3D FastEigen3x3 (geometry/EstimateNormals.cpp)
 // Robust closed-form eigenvector of the smallest eigenvalue (Geometric Tools).
@@ -628,10 +639,7 @@ Mat4 toldi_frame(const Cloud& cloud, const KDTree& tree, const Vec3& central_poi
             for (int c = 0; c < 3; c++) cov.m[r][c] += v[r] * v[c];
     }
     // ISR.cpp:275-281 eigenvector of the smallest eigenvalue
-    double w[3];
-    Mat3 V;
-    sym_eig3(cov, w, V);
-    Vec3 n(V.m[0][0], V.m[1][0], V.m[2][0]);
+    Vec3 n = sym_eig3_smallest(cov);
     // ISR.cpp:286-298
     Vec3 acc(0, 0, 0), acc_s(0, 0, 0);
     for (int i = 1; i < (int)indices.size(); i++) {
@@ -1283,6 +1291,31 @@ int refcpu_gicp_covariances(const double* normals, int64_t n, double eps, double
         Mat3 r = mul(mul(Rx, C), transpose(Rx));
         for (int a = 0; a < 3; a++)
             for (int b = 0; b < 3; b++) cov[i * 9 + a * 3 + b] = r.m[a][b];
+    }
+    return 0;
+}
+
+namespace {
+Mat3 sym_from6(const double* a) {
+    Mat3 A;
+    A.m[0][0] = a[0]; A.m[0][1] = A.m[1][0] = a[1]; A.m[0][2] = A.m[2][0] = a[2];
+    A.m[1][1] = a[3]; A.m[1][2] = A.m[2][1] = a[4]; A.m[2][2] = a[5];
+    return A;
+}
+}  // namespace
+
+int refcpu_sym_eig3_smallest(const double* a, int64_t n, double* vec) {
+    for (int64_t i = 0; i < n; i++) {
+        const Vec3 v = sym_eig3_smallest(sym_from6(a + 6 * i));
+        vec[3 * i] = v.x; vec[3 * i + 1] = v.y; vec[3 * i + 2] = v.z;
+    }
+    return 0;
+}
+
+int refcpu_fast_eigen3x3(const double* a, int64_t n, double* vec) {
+    for (int64_t i = 0; i < n; i++) {
+        const Vec3 v = FastEigen3x3(sym_from6(a + 6 * i));
+        vec[3 * i] = v.x; vec[3 * i + 1] = v.y; vec[3 * i + 2] = v.z;
     }
     return 0;
 }

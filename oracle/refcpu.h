@@ -115,6 +115,13 @@ int refcpu_estimate_normals(const double* pts, int64_t n, int k, double* normals
  * (ISR.cpp:45-51).  cov out [n*9] row-major */
 int refcpu_gicp_covariances(const double* normals, int64_t n, double eps, double* cov);
 
+/* The two 3x3 symmetric eigen-solvers on their own, one matrix "a00 a01 a02 a11 a12 a22"
+ * per row of a [n*6]: the eigenvector of the smallest eigenvalue by the cyclic Jacobi that
+ * stands for Eigen::SelfAdjointEigenSolver (ISR.cpp:275-281; unit length), and Open3D's FastEigen3x3
+ * (zero for the zero matrix, as Open3D returns it).  vec out [n*3] */
+int refcpu_sym_eig3_smallest(const double* a, int64_t n, double* vec);
+int refcpu_fast_eigen3x3(const double* a, int64_t n, double* vec);
+
 /* Exact 1-NN of each query in D dims (D = 3 or 12) with nanoflann L2 arithmetic,
  * tie-break lowest index.  ISR.cpp:402-416 (D=3), 444-470 (D=12). */
 int refcpu_nn(const double* query, int64_t nq, const double* data, int64_t nd, int dim,

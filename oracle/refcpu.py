@@ -86,6 +86,8 @@ def lib():
         L.refcpu_toldi_frames.argtypes = [dp, C.c_int64, C.c_int, dp]
         L.refcpu_estimate_normals.argtypes = [dp, C.c_int64, C.c_int, dp]
         L.refcpu_gicp_covariances.argtypes = [dp, C.c_int64, C.c_double, dp]
+        L.refcpu_sym_eig3_smallest.argtypes = [dp, C.c_int64, dp]
+        L.refcpu_fast_eigen3x3.argtypes = [dp, C.c_int64, dp]
         L.refcpu_nn.argtypes = [dp, C.c_int64, dp, C.c_int64, C.c_int, ip, dp]
         L.refcpu_estimate.argtypes = [C.c_int, dp, dp, dp, dp, dp, ip, C.c_int64, dp, dp]
         L.refcpu_trim.argtypes = [fp, C.c_int64, C.c_double, ip]
@@ -194,6 +196,23 @@ def gicp_covariances(normals, eps=1e-3):
     normals = np.ascontiguousarray(normals, dtype=np.float64)
     out = np.zeros((normals.shape[0], 3, 3))
     lib().refcpu_gicp_covariances(_d(normals), normals.shape[0], eps, _d(out))
+    return out
+
+
+def sym_eig3_smallest(a6):
+    """Smallest eigenvector of every symmetric matrix (rows a00 a01 a02 a11 a12 a22) by the
+    Jacobi solver of the TOLDI z axis: (n, 3)."""
+    a6 = np.ascontiguousarray(a6, dtype=np.float64).reshape(-1, 6)
+    out = np.zeros((a6.shape[0], 3))
+    lib().refcpu_sym_eig3_smallest(_d(a6), a6.shape[0], _d(out))
+    return out
+
+
+def fast_eigen3x3(a6):
+    """Open3D FastEigen3x3 of every symmetric matrix (rows a00 a01 a02 a11 a12 a22): (n, 3)."""
+    a6 = np.ascontiguousarray(a6, dtype=np.float64).reshape(-1, 6)
+    out = np.zeros((a6.shape[0], 3))
+    lib().refcpu_fast_eigen3x3(_d(a6), a6.shape[0], _d(out))
     return out
 
 

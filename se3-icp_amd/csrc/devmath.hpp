@@ -1,4 +1,6 @@
-// devmath.hpp — f64 small-matrix math used by the setup kernels (device only).
+// devmath.hpp — f64 small-matrix math used by the setup kernels.  The solvers are
+// __host__ __device__ plain arithmetic, so tests/devmath_host.cpp builds the same source
+// for the host (tests/test_devmath_host.py).
 //
 // Restates, for the GPU, the third-party arithmetic the reference calls per point:
 //   * Eigen::SelfAdjointEigenSolver<Matrix3d> (TOLDI normal, ISR.cpp:275-281)
@@ -11,18 +13,18 @@
 namespace se3icp {
 
 struct d3 { double x, y, z; };
-__device__ __forceinline__ d3 mk3(double a, double b, double c) { return d3{a, b, c}; }
-__device__ __forceinline__ d3 operator-(d3 a, d3 b) { return d3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ d3 operator+(d3 a, d3 b) { return d3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ d3 operator*(double s, d3 a) { return d3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot3(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ d3 cross3(d3 a, d3 b) {
+__host__ __device__ __forceinline__ d3 mk3(double a, double b, double c) { return d3{a, b, c}; }
+__host__ __device__ __forceinline__ d3 operator-(d3 a, d3 b) { return d3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__host__ __device__ __forceinline__ d3 operator+(d3 a, d3 b) { return d3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__host__ __device__ __forceinline__ d3 operator*(double s, d3 a) { return d3{s * a.x, s * a.y, s * a.z}; }
+__host__ __device__ __forceinline__ double dot3(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__host__ __device__ __forceinline__ d3 cross3(d3 a, d3 b) {
     return d3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
 // Symmetric 3x3 eigen-decomposition by cyclic Jacobi rotations.  a is symmetric
 // (row-major, only a[0..8] used); returns eigenvector of the smallest eigenvalue.
-__device__ inline d3 jacobi_smallest_evec(double a00, double a01, double a02, double a11, double a12, double a22) {
+__host__ __device__ inline d3 jacobi_smallest_evec(double a00, double a01, double a02, double a11, double a12, double a22) {
     double a[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
     double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     for (int sweep = 0; sweep < 32; ++sweep) {
@@ -65,12 +67,16 @@ __device__ inline d3 jacobi_smallest_evec(double a00, double a01, double a02, do
     const bool m1 = a[1][1] < a[0][0];
     const bool m2 = a[2][2] < (m1 ? a[1][1] : a[0][0]);
     const double w2 = m2 ? 1.0 : 0.0, w1 = (!m2 && m1) ? 1.0 : 0.0, w0 = 1.0 - w1 - w2;
-    return d3{w0 * v[0][0] + w1 * v[0][1] + w2 * v[0][2], w0 * v[1][0] + w1 * v[1][1] + w2 * v[1][2],
-              w0 * v[2][0] + w1 * v[2][1] + w2 * v[2][2]};
+    const d3 n{w0 * v[0][0] + w1 * v[0][1] + w2 * v[0][2], w0 * v[1][0] + w1 * v[1][1] + w2 * v[1][2],
+               w0 * v[2][0] + w1 * v[2][1] + w2 * v[2][2]};
+    // at unit length: where the two smallest eigenvalues coincide the sweeps keep rotating
+    // rounding noise within their plane up to the sweep limit, and the accumulated column
+    // drifts by about an eps per rotation (13 eps after 32 sweeps); Eigen's vectors are unit
+    return (1.0 / sqrt(dot3(n, n))) * n;
 }
 
 // Open3D FastEigen3x3 helpers (Geometric Tools "RobustEigenSymmetric3x3").
-__device__ inline d3 fe_evec0(const double A[3][3], double eval0) {
+__host__ __device__ inline d3 fe_evec0(const double A[3][3], double eval0) {
     const d3 row0{A[0][0] - eval0, A[0][1], A[0][2]};
     const d3 row1{A[0][1], A[1][1] - eval0, A[1][2]};
     const d3 row2{A[0][2], A[1][2], A[2][2] - eval0};
@@ -84,7 +90,7 @@ __device__ inline d3 fe_evec0(const double A[3][3], double eval0) {
     if (imax == 1) return (1.0 / sqrt(d1)) * r0xr2;
     return (1.0 / sqrt(d2)) * r1xr2;
 }
-__device__ inline d3 fe_evec1(const double A[3][3], d3 e0, double eval1) {
+__host__ __device__ inline d3 fe_evec1(const double A[3][3], d3 e0, double eval1) {
     d3 U;
     if (fabs(e0.x) > fabs(e0.y)) {
         const double il = 1 / sqrt(e0.x * e0.x + e0.z * e0.z);
@@ -118,7 +124,7 @@ __device__ inline d3 fe_evec1(const double A[3][3], d3 e0, double eval1) {
     return U;
 }
 // Open3D FastEigen3x3: eigenvector of the smallest eigenvalue of a covariance.
-__device__ inline d3 fast_eigen3x3(double c00, double c01, double c02, double c11, double c12, double c22) {
+__host__ __device__ inline d3 fast_eigen3x3(double c00, double c01, double c02, double c11, double c12, double c22) {
     double A[3][3] = {{c00, c01, c02}, {c01, c11, c12}, {c02, c12, c22}};
     double mc = A[0][0];
 #pragma unroll

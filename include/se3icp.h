@@ -250,7 +250,9 @@ int se3icp_register_graph_report_device(int device, int32_t n_clouds, const doub
  * SE3ICP_ERR_INVALID_ARG) = {distinct clouds some edge uses, uses (2 * n_pairs), classes,
  * classes that ran a full neighbour selection, queries adopted, queries rejected by order,
  * queries rejected by gap, queries without a list (the last four: adoption, always 0),
- * bytes uploaded}. */
+ * bytes uploaded}.  A class whose selection started from a sibling's neighbour distances
+ * (se3icp_set_lrf_seeding, below) ran a full, self-certifying selection and counts as one: it
+ * adopted nothing. */
 #define SE3ICP_GRAPH_STATS_N 9
 int se3icp_last_graph_stats(int device, int64_t* out, int n);
 
@@ -272,11 +274,37 @@ int se3icp_last_graph_stats(int device, int64_t* out, int n);
  * plain batch), 2 one selection per class.  Anything else is SE3ICP_ERR_INVALID_ARG, checked
  * before the device is looked up.  The setting is the engine's (device | slot << 8) and holds
  * until it is set again.  Neighbour-set adoption between the classes of one cloud is not
- * built here either.  The host-pointer entries and the sweeps do not look: a caller with host
+ * built here either; what a cloud's later classes do take from its first is a starting bound
+ * for their own selection (se3icp_set_lrf_seeding, below).  The host-pointer entries and the sweeps do not look: a caller with host
  * buffers has se3icp_register_graph, which also uploads every cloud once.
  * se3icp_last_graph_stats after a device batch at level 0 or 2: {distinct clouds, slots,
  * classes, classes that selected, 0, 0, 0, 0, 0}. */
 int se3icp_set_batch_sharing(int device, int level);
+
+/* Seeding.  Where a cloud has several classes (se3icp_register_graph at sharing >= 2, a device
+ * batch that found a shared cloud) under the run_se3_* normalization, they differ in the pair's
+ * scale only: every squared distance of a later class is (s_b / s_a)^2 times the first class's
+ * up to rounding.  The cloud's first selecting class stores each point's Kw-th neighbour
+ * distance and a later class starts its selection from the bound that gives instead of from
+ * infinity.  The later class still runs a full selection in its own arithmetic, and that
+ * selection certifies itself (its closing bound must come out at or below the seeded one, else
+ * its queries go to the exact kernel): no neighbour set is taken over, a wrong seed costs time
+ * and never a result, and results are bitwise the unseeded ones.  So a seeded class counts in
+ * `classes that ran a full neighbour selection` of se3icp_last_graph_stats, whose nine values
+ * keep their meaning and whose four adoption counters stay 0.
+ * mode: 0 seeded (the default of every engine), 1 off, 2 every seed halved before use (a
+ * diagnostic: the certificate fails and the exact kernel takes the queries), 3 every seed
+ * multiplied by 4 (a diagnostic: loose seeds).  Anything else is SE3ICP_ERR_INVALID_ARG, checked
+ * before the device is looked up.  The setting is the engine's (device | slot << 8).  The
+ * host-pointer batch entries, the sweeps and the se3icp_set_lrf_exact modes do not seed. */
+int se3icp_set_lrf_seeding(int device, int mode);
+/* Of the last registration call on `device`: out[SE3ICP_SEED_STATS_N], n >= that (else
+ * SE3ICP_ERR_INVALID_ARG) = {classes seeded, queries of wavefronts that started from a seed,
+ * queries of wavefronts of seeded classes that ran without one (a neighbour's seed absent: the
+ * first class handed that point to the exact kernel; a cloud's last, partial, wavefront),
+ * queries handed to the exact kernel after a failed certificate}. */
+#define SE3ICP_SEED_STATS_N 4
+int se3icp_last_seed_stats(int device, int64_t* out, int n);
 
 /* ------------------------------------------------------------- registration reports
  * What says whether a pose is any good, evaluated at the FINAL pose as Open3D's

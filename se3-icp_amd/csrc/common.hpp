@@ -24,6 +24,10 @@ constexpr int kStatCols = 17;     // columns of the device work-counter table (V
 // NN work: occupied (query, target) distance evaluations of the SE(3) / R3 searches (the
 // lane-evaluation slots they issue are columns 0 and 2)
 constexpr int kStatUseSe3 = 15, kStatUseR3 = 16;
+// setup (the table is cleared between the setup and the loop): k_lrf8's launch of seeded
+// clouds counts in columns kSeedStatCol .. + 2 the queries of waves that started from a seed,
+// that ran without one (an absent seed; a wave the exact kernel takes whole), whose seed failed
+constexpr int kSeedStatCol = 14;
 constexpr int kHist = 256;        // pose history ring of the loop (View::hist), iterations
 constexpr int kTrimList = 4096;   // k_trim: LDS key list / window capacity per pair
 constexpr int kTrimBlocks = 32;   // k_trim_window: blocks per pair

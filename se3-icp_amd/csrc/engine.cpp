@@ -489,19 +489,38 @@ int Engine::setup_knn(hipStream_t s) {
             // eight queries per wavefront; the few it cannot resolve from f32 keys (and every
             // query of a cloud whose k it cannot hold) go to the exact kernels
             // waves aligned to each cloud's first point (results independent of the batch)
-            std::vector<int32_t> wb(nclouds_ + 1, 0);
+            // Two wave tables: the seeded clouds of select_by_class (graph.hpp, graph_plan_seeds)
+            // run in a launch of their own behind the one that stores their seeds.
+            const bool seeding = seed_on_;
+            const int nt = nclouds_ + 1;
+            std::vector<int32_t> wb(2 * (size_t)nt, 0);
             // (a cloud that wants no neighbours gets no waves: the kernel's search for a wave's
             // cloud takes the last one that starts at or before it)
-            for (int c = 0; c < nclouds_; ++c) wb[c + 1] = wb[c] + (h_setup_[c].k_knn > 0 ? (h_clouds_[c].n + 7) / 8 : 0);
-            const int nw = wb[nclouds_];
-            if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * nw + 64) || !ensure<int32_t>(d_lrf_fbn_, 2 + nclouds_ + 1))
+            for (int c = 0; c < nclouds_; ++c) {
+                const int waves = h_setup_[c].k_knn > 0 ? (h_clouds_[c].n + 7) / 8 : 0;
+                const bool sd = seeding && seed_ref_[c].load >= 0;
+                wb[c + 1] = wb[c] + (sd ? 0 : waves);
+                wb[nt + c + 1] = wb[nt + c] + (sd ? waves : 0);
+            }
+            const int nw = wb[nclouds_], nw_sd = wb[nt + nclouds_];
+            if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * (nw + nw_sd) + 64) || !ensure<int32_t>(d_lrf_fbn_, 2 + 2 * (size_t)nt))
                 return SE3ICP_ERR_OUT_OF_MEMORY;
             int32_t* d_wb = (int32_t*)d_lrf_fbn_.p + 2;
             int32_t* fb = (int32_t*)d_lrf_fb_.p;
             int32_t* fbn = (int32_t*)d_lrf_fbn_.p;
             HIPCHK(hipMemsetAsync(fbn, 0, 2 * sizeof(int32_t), s));
-            HIPCHK(hipMemcpyAsync(d_wb, wb.data(), sizeof(int32_t) * (nclouds_ + 1), hipMemcpyHostToDevice, s));
-            launch_lrf8(v, d_wb, 0, nw, fb, fbn, s);
+            HIPCHK(hipMemcpyAsync(d_wb, wb.data(), sizeof(int32_t) * 2 * nt, hipMemcpyHostToDevice, s));
+            if (seeding) {
+                if (!ensure<float>(d_seed_, (size_t)seed_floats_) || !ensure<SeedRef>(d_seed_ref_, nclouds_))
+                    return SE3ICP_ERR_OUT_OF_MEMORY;
+                HIPCHK(hipMemsetAsync(d_seed_.p, 0xff, sizeof(float) * (size_t)seed_floats_, s));  // all ones: absent
+                HIPCHK(hipMemcpyAsync(d_seed_ref_.p, seed_ref_.data(), sizeof(SeedRef) * nclouds_, hipMemcpyHostToDevice, s));
+                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s, (const SeedRef*)d_seed_ref_.p, (float*)d_seed_.p, false, lrf_seeding_);
+                launch_lrf8(v, d_wb + nt, 0, nw_sd, fb, fbn, s, (const SeedRef*)d_seed_ref_.p, (float*)d_seed_.p, true,
+                            lrf_seeding_);
+            } else {
+                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s);
+            }
             launch_lrf_list(v, fb, fbn, s);
             big(fb, fbn, kSmallK);
         }
@@ -532,6 +551,11 @@ int Engine::read_lrf_stats() {
     ktimes_.lrf_box_tests = sum[3];
     ktimes_.lrf_candidates = sum[4];
     ktimes_.lrf_fallback = sum[6];
+    for (int k = 0; k < 3; ++k) {  // k_lrf8's launch of seeded clouds (integers, summed as such)
+        unsigned long long q = 0;
+        for (int i = 0; i < kStatSlots; ++i) q += h_lrf_stats_[kStatCols * i + kSeedStatCol + k];
+        seed_stats_[1 + k] = (int64_t)q;
+    }
 #ifdef SE3ICP_PROF
     tree_prof_report();
     std::fprintf(stderr, "[prof] k_lrf cycles/query: knn|scan %.0f sort|tighten %.0f sums|final+sums %.0f finish %.0f "
@@ -586,6 +610,7 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     HIPCHK(hipSetDevice(dev_));
     c->s = user_stream ? user_stream : stream_;
     ktimes_ = KernelTimes{};
+    for (int64_t& x : seed_stats_) x = 0;
     // phase times on the GPU timeline (the host does not wait for the setup): events
     // 12 (begin), 13 (setup done), 14 (loop done)
     HIPCHK(hipEventRecord(ev_[12], c->s));
@@ -783,9 +808,42 @@ int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>
     }
     const int nchS = (int)sel_chunks_.size();
     if (!ensure<ChunkWork>(g_chunks_, nchS) || !ensure<GraphSeg>(g_seg_, U)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    // seeding: a cloud's later classes start from its first class's neighbour distances
+    // (graph_plan_seeds; k_lrf8 only, so not under se3icp_set_lrf_exact)
+    seed_ref_.clear();
+    seed_floats_ = 0;
+    if (lrf_seeding_ != 1 && lrf_exact_only_ == 0 && !knn_list_) {
+        std::vector<int32_t> kk(K);
+        std::vector<int64_t> nn(K);
+        for (int k = 0; k < K; ++k) {
+            kk[k] = sel_run_[home[k]].k_knn;
+            nn[k] = h_clouds_[home[k]].n;
+        }
+        std::vector<SeedClass> sc;
+        const int seeded = graph_plan_seeds(plan, kk.data(), nn.data(), &sc);
+        int64_t total = 0;
+        for (int k = 0; k < K; ++k)
+            if (sc[k].from >= 0) total += nn[k];  // (an upper bound of the buffer: a source may seed several)
+        if (seeded > 0 && total <= INT32_MAX) {
+            seed_ref_.assign(U, SeedRef{-1, -1, 1.0});
+            for (int k = 0; k < K; ++k) {
+                if (sc[k].from < 0) continue;
+                SeedRef& src = seed_ref_[home[sc[k].from]];
+                if (src.store < 0) {
+                    src.store = (int32_t)seed_floats_;
+                    seed_floats_ += nn[k];
+                }
+                seed_ref_[home[k]].load = src.store;
+                seed_ref_[home[k]].rho2 = sc[k].rho2;
+            }
+            seed_stats_[0] = seeded;
+            seed_on_ = true;
+        }
+    }
     h_setup_ = sel_run_;
     HIPCHK(hipMemcpyAsync(d_setup_.p, sel_run_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
     const int rc = setup_knn(s);
+    seed_on_ = false;  // (seed_ref_ itself stays: the copy that reads it may still be queued)
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     // the batch's own table from here on (the copies below read cf_target of the use itself)

@@ -88,6 +88,7 @@ class Engine {
     void set_lrf_exact(int mode) { lrf_exact_only_ = mode; }
     void set_nn_events(bool on) { nn_events_ = on; }
     void set_batch_sharing(int level) { batch_sharing_ = level; }
+    void set_lrf_seeding(int mode) { lrf_seeding_ = mode; }
     const KernelTimes& kernel_times() const { return ktimes_; }
 
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
@@ -112,6 +113,10 @@ class Engine {
     // [GS_COUNT] of the last register_graph, or of the last device batch that looked for shared
     // clouds (setup_pairs_shared)
     const int64_t* graph_stats() const { return graph_stats_; }
+    // [4] of the last registration call (se3icp_last_seed_stats): classes seeded, queries of
+    // waves that started from a seed, that ran without one, that were handed over after a
+    // failed certificate
+    const int64_t* seed_stats() const { return seed_stats_; }
 
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
@@ -229,6 +234,9 @@ class Engine {
     bool nn_events_ = true;
     // se3icp_set_batch_sharing: 0 the highest level built (= 2), 1 off, 2 one selection per class
     int batch_sharing_ = 0;
+    // se3icp_set_lrf_seeding: 0 a cloud's later classes start their selection from its first
+    // class's neighbour distances (default), 1 off, 2 / 3 diagnostics: every seed halved / times 4
+    int lrf_seeding_ = 0;
     se3icp_trace* trace_ = nullptr;      // armed per-iteration record of one pair (se3icp_set_trace)
     int record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t s);
     double trace_prev_[kStatCols] = {};
@@ -274,6 +282,13 @@ class Engine {
     std::vector<ChunkWork> sel_chunks_;
     std::vector<GraphSeg> sel_seg_;
     int64_t graph_stats_[9] = {};
+    // select_by_class -> setup_knn: whether this selection seeds, where each use stores / reads
+    // seeds, the floats of the seed buffer, and the buffers on the device
+    bool seed_on_ = false;
+    std::vector<SeedRef> seed_ref_;
+    int64_t seed_floats_ = 0;
+    DevBuf d_seed_{bufs_}, d_seed_ref_{bufs_};
+    int64_t seed_stats_[4] = {};
     Pinned<PairDev> h_pairs_{pins_};
     Pinned<double> h_red_{pins_}, h_partial_{pins_};
     Pinned<int32_t> h_rechecked_{pins_};

@@ -61,6 +61,7 @@ struct GraphClass {
 struct GraphPlan {
     std::vector<int32_t> use_class;  // [2P]: class of use 2p (source) and 2p + 1 (target)
     std::vector<GraphClass> classes; // in order of first use
+    bool normalize = false, dedupe = false;  // as graph_plan_uses was asked
 };
 
 // A use as the planner sees it: its cloud, the EstimateNormals k it asks for and the
@@ -93,6 +94,8 @@ inline void graph_plan_uses(int32_t n_uses, const GraphUse* use, bool normalize,
     std::map<Key, int32_t> seen;
     plan->use_class.assign((size_t)n_uses, -1);
     plan->classes.clear();
+    plan->normalize = normalize;
+    plan->dedupe = dedupe;
     for (int32_t u = 0; u < n_uses; ++u) {
         GraphClass g{};
         g.cloud = use[u].cloud;
@@ -133,6 +136,53 @@ inline void graph_plan_uses(int32_t n_uses, const GraphUse* use, bool normalize,
         if (it == owner.end()) owner[g.cloud] = k;
         else if (plan->classes[it->second].k_nrm == g.k_nrm) g.nrm_from = it->second;
     }
+}
+
+// ---- seeding the selection of a cloud's later classes (Engine::select_by_class, k_lrf8.hip)
+// Under the run_se3_* normalization the classes of one cloud are fl(fl(p - c) * s) of the same
+// fl(p - c) for different pair scales s, so every squared distance in class b is
+// (s_b / s_a)^2 times class a's up to f64 rounding.  The cloud's first selecting class (the
+// source) stores every point's Kw-th neighbour distance and a later class starts its own, full
+// and self-certifying selection from rho2 times that instead of from infinity.
+// se3icp_set_lrf_seeding
+constexpr int kLrfSeedingMin = 0, kLrfSeedingMax = 3;
+struct SeedClass {
+    int32_t from;  // the class whose stored distances seed this one (-1: selects unseeded)
+    double rho2;   // (own norm_scale / the source's)^2
+};
+// k_knn [classes]: the neighbours the class's selection asks for (0: it selects nothing);
+// n_pts [classes]: the points of its cloud.  Per cloud the first class that selects is the
+// source; a later class is seeded from it when it selects, was centred with the same bits, has
+// its f32 copy uncentred (as the source has) and asks for no more neighbours, Kw = min(k_knn, n),
+// than the source found.  Nothing is seeded without the normalization or with a class per use
+// (sharing level 1).  Returns the seeded classes.
+inline int32_t graph_plan_seeds(const GraphPlan& plan, const int32_t* k_knn, const int64_t* n_pts,
+                                std::vector<SeedClass>* seed) {
+    const int32_t K = (int32_t)plan.classes.size();
+    seed->assign((size_t)K, SeedClass{-1, 1.0});
+    if (!plan.normalize || !plan.dedupe) return 0;
+    auto uncentred = [](const GraphClass& g) { return g.f32_center[0] == 0.0 && g.f32_center[1] == 0.0 && g.f32_center[2] == 0.0; };
+    std::map<int32_t, int32_t> source;  // cloud -> its first class that selects
+    int32_t seeded = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        if (k_knn[k] <= 0) continue;
+        const GraphClass& g = plan.classes[k];
+        auto it = source.find(g.cloud);
+        if (it == source.end()) {
+            source[g.cloud] = k;
+            continue;
+        }
+        const int32_t a = it->second;
+        const GraphClass& ga = plan.classes[a];
+        const int64_t kw = k_knn[k] < n_pts[k] ? k_knn[k] : n_pts[k], kwa = k_knn[a] < n_pts[a] ? k_knn[a] : n_pts[a];
+        const double rho = g.norm_scale / ga.norm_scale;
+        if (std::memcmp(g.norm_center, ga.norm_center, sizeof(g.norm_center)) != 0 || !uncentred(g) || !uncentred(ga) ||
+            n_pts[k] != n_pts[a] || kw > kwa || !(rho > 0.0) || !std::isfinite(rho * rho))
+            continue;
+        (*seed)[k] = SeedClass{a, rho * rho};
+        ++seeded;
+    }
+    return seeded;
 }
 
 // Plan the classes of P edges over clouds the caller names.

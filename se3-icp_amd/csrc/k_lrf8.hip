@@ -284,6 +284,9 @@ __device__ __forceinline__ uint3 tighten_group_sorted(unsigned* lists, int g, in
     const unsigned tg = nbg >= Kw ? widen_bound(kth_of_two(list, mv, B, nb, Kw - 1) | kIdBits, S) : kAll;
     const int ka = upper_count(list, mv, tg), kb = upper_count(B, nb, tg);
     const int kept = ka + kb;
+    // (wave-uniform) every list was sorted whole just now and has no tail: the kept set is its
+    // first ka entries as they lie -- a seeded wave's closing tightening
+    if (presort && tail_per == 0) return make_uint3(tg, (unsigned)ka, (unsigned)ka);
     if (__ballot(kept > 128) == 0ull) {
         unsigned k[16];
         load_head<16>(list, ka, l, k);
@@ -485,12 +488,26 @@ __device__ __forceinline__ bool final_group(unsigned* lists, const int* leaf_slo
 
 static_assert(kW >= 2 && kW * kQ <= 64, "the per-block epilogue: waves 0 and 1, a lane per query");
 
+// Seeding.  Two classes of one cloud differ in the pair's scale only, so the
+// squared distance of a point's Kw-th neighbour in one is (s_b / s_a)^2 times the other's up to
+// rounding.  ST = true: a wave of a cloud with seed[c].store >= 0 stores the f32 key of every
+// query's Kw-th neighbour (queries it hands over store nothing); a call that seeds nothing
+// runs ST = false, the kernel as it was before seeding.  SD = true, a launch of
+// seeded clouds only: a wave whose eight queries all find a stored key starts from the bound it
+// gives instead of from the accept-all fill, collects what lies within it and closes with one
+// tightening, which is the wave's certificate: the list's own bound, widen_bound(Kw-th key),
+// must come out at or below the bound the lists were collected under.  Then the lists are
+// complete for it, as an unseeded wave's are; otherwise (a seed that was too small) the eight
+// queries go to the exact kernel.  The seed is a hint: it costs time when wrong, never a result.
+//
 // waves per SIMD: 6 = the LDS limit (26.6 KB per block); A/B 4 -> 5 -> 6: 6.73 -> 6.45 -> 6.38 ms
+template <bool SD, bool ST>
 __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <= 192 ? 6 : (kCap <= 224 ? 5 : 4)))) void k_lrf8(
     View v, const int32_t* __restrict__ cloud_of, const CloudSetup* __restrict__ setup,
     const CloudDev* __restrict__ clouds, const float* __restrict__ tlo, const float* __restrict__ thi,
     const double4* __restrict__ P4, const int32_t* __restrict__ wave_base, int w_lo, int nwaves,
-    int32_t* __restrict__ fb_list, int32_t* __restrict__ fb_count) {
+    int32_t* __restrict__ fb_list, int32_t* __restrict__ fb_count, const SeedRef* __restrict__ seed,
+    float* __restrict__ seedbuf, int seed_mode) {
     // (a query's park overlays the tail of its list, free once the list is final: <= 128 entries)
     __shared__ __attribute__((aligned(16))) unsigned s_list[kW][kQ][kStride];
     auto park_of = [&](int w, int j) __attribute__((always_inline)) {
@@ -594,6 +611,36 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
         }
         n_q = kQ;
     }
+    // seeded waves: sd_open until the closing tightening is queued, sd_close while it runs;
+    // t_cert: the last tightening's bounds all came out at or below the bounds before it
+    bool sd_open = false, sd_close = false, t_cert = true;
+    unsigned n_sdq = 0, n_sda = 0, n_sdf = 0;
+    if constexpr (SD) {
+        if (mode == 2) n_sda = (unsigned)qn;
+        if (mode == 1) {
+            const SeedRef sr = seed[c];
+            // the stored keys of the eight queries, by local point index (the two classes'
+            // trees order tied points differently)
+            float sv = 0.f;
+            if (lane < kQ) sv = seedbuf[sr.load + T.perm[w0 + lane]];
+            if (seed_mode == 2) sv *= 0.5f;
+            if (seed_mode == 3) sv *= 4.f;
+            // (an absent seed is all ones, a NaN: the whole wave then runs unseeded)
+            if (__ballot(!(bool)((int)(sv >= 0.f) & (int)(sv < INFINITY))) == 0ull) {
+                // the Kw-th exact distance under this class's scale, rounded up; widened once
+                // to cover the Kw-th list key (an f32 distance of the f32 points, cut) and once
+                // more as every bound is, so that the closing tightening's bound lies below it
+                const unsigned t0 = f32_up_bits((double)sv * sr.rho2 * (1.0 + 0x1p-20)) | kIdBits;
+                const unsigned tb = widen_bound(widen_bound(t0, s_norm), s_norm);
+#pragma unroll
+                for (int j = 0; j < kQ; ++j) Tq[j] = (unsigned)__builtin_amdgcn_readlane((int)tb, j);
+                sd_open = true;
+                n_sdq = kQ;
+            } else {
+                n_sda = kQ;
+            }
+        }
+    }
 
     // ---------------------------------------------------------------- bound tightening
     auto tighten = [&]() __attribute__((always_inline)) {
@@ -615,10 +662,25 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
         const uint3 r3 = tighten_group_sorted(lists, g, l, (int)group_len(), mvv, (int)nmax, Kw, presort, tail_per, s_norm);
         mvv = (int)r3.z;
         __builtin_amdgcn_wave_barrier();
+        if constexpr (SD) {
+            // a list is complete for the smallest bound it was collected under: a bound never
+            // grows (an unseeded wave's never does; a seeded wave's list may be short of Kw
+            // entries, or its Kw-th key sit right at the seeded bound, whose widening exceeds it)
+            bool cert = true;
 #pragma unroll
-        for (int j = 0; j < kQ; ++j) {
-            Tq[j] = (unsigned)__builtin_amdgcn_readlane((int)r3.x, 8 * j);
-            nbq[j] = (unsigned)__builtin_amdgcn_readlane((int)r3.y, 8 * j);
+            for (int j = 0; j < kQ; ++j) {
+                const unsigned tn = (unsigned)__builtin_amdgcn_readlane((int)r3.x, 8 * j);
+                cert &= tn <= Tq[j];
+                Tq[j] = min(Tq[j], tn);
+                nbq[j] = (unsigned)__builtin_amdgcn_readlane((int)r3.y, 8 * j);
+            }
+            t_cert = cert;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kQ; ++j) {
+                Tq[j] = (unsigned)__builtin_amdgcn_readlane((int)r3.x, 8 * j);
+                nbq[j] = (unsigned)__builtin_amdgcn_readlane((int)r3.y, 8 * j);
+            }
         }
     };
 
@@ -731,6 +793,9 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
         int cur = -1, part = 0;
         bool do_tighten = false, retried = false;
         float tf = INFINITY;  // f32 box-test bound of the union of the eight (set with each tightening)
+        if constexpr (SD) {
+            if (sd_open) tf = thr_f();  // (a seeded wave has bounds from the start)
+        }
         while (!fb_wave) {
             if (do_tighten) {
                 PROF8_NOW(t_t0);
@@ -738,6 +803,16 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
                 PROF8_NOW(t_t1);
                 PROF8_ADD(c_tight, t_t0, t_t1);
                 do_tighten = false;
+                if constexpr (SD) {
+                    if (sd_close) {  // the seeded wave's certificate
+                        sd_close = false;
+                        if (!t_cert) {
+                            fb_wave = true;
+                            n_sdf = kQ;
+                            continue;
+                        }
+                    }
+                }
                 tf = thr_f();  // the box-test bound changes only here
 #if defined(SE3ICP_LRF8_CUT) && SE3ICP_LRF8_CUT == 4
                 if (stage == 2) break;  // (measurement build: stop after the first bound)
@@ -769,7 +844,9 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
             int leaf = -1;
             if (stage == 0) {
                 leaf = nxt++;
-                if (nxt > lf1) stage = 1;
+                // (a seeded wave needs no accept-all fill and no first tightening: on to the
+                // leaves within its bounds, s_lo .. s_hi being the queries' own)
+                if (nxt > lf1) stage = (SD && sd_open) ? 2 : 1;
             } else if (stage == 1) {
                 // (filling the lists beyond Kw while a whole leaf still fits: the first
                 // bound, the Kw-th of more nearby points, is tighter)
@@ -788,6 +865,15 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
             } else if (stage == 2) {
                 if (!haveA) {
                     if (c0 >= nA) {  // done; the final sort takes lists of <= 128: tighten once more
+                        if constexpr (SD) {
+                            if (sd_open) {  // a seeded wave always closes with a tightening
+                                sd_open = false;
+                                sd_close = true;
+                                do_tighten = true;
+                                retried = true;
+                                continue;
+                            }
+                        }
                         unsigned nmax = 0;
 #pragma unroll
                         for (int j = 0; j < kQ; ++j) nmax = max(nmax, nbq[j]);
@@ -889,6 +975,17 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
     // (their live registers do not add up).
     const unsigned* rl = lists + g * kStride;
     double* pj = park_of(wid, g);
+    if constexpr (ST) {
+        // the seed of the cloud's later classes: the f32 key of rank Kw - 1 (final_group's key
+        // of that rank; tied ranks share it), by local point index
+        if (mode == 1) {
+            const int so = seed[c].store;
+            if ((int)(so >= 0) & (int)mine & (int)(l == 0)) {
+                const p3 f = ld3(P4, (int)rl[Kw - 1]);
+                seedbuf[so + T.perm[wq]] = (float)l2_3(qg.x, qg.y, qg.z, f.x, f.y, f.z);
+            }
+        }
+    }
     {
         double x[12];
 #pragma unroll
@@ -973,6 +1070,11 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
         atomicAdd(ctr + 1, (unsigned long long)n_leaves);
         atomicAdd(ctr + 2, (unsigned long long)n_sel);
         atomicAdd(ctr + 4, (unsigned long long)n_cand);
+        if constexpr (SD) {
+            if (n_sdq) atomicAdd(ctr + kSeedStatCol, (unsigned long long)n_sdq);
+            if (n_sda) atomicAdd(ctr + kSeedStatCol + 1, (unsigned long long)n_sda);
+            if (n_sdf) atomicAdd(ctr + kSeedStatCol + 2, (unsigned long long)n_sdf);
+        }
     }
 
 #if defined(SE3ICP_LRF8_CUT) && SE3ICP_LRF8_CUT == 3
@@ -1110,11 +1212,18 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
 }  // namespace
 
 void launch_lrf8(const View& v, const int32_t* wave_base, int w_lo, int w_hi, int32_t* fb_list, int32_t* fb_count,
-                 hipStream_t s) {
+                 hipStream_t s, const SeedRef* seed, float* seedbuf, bool seeded, int seed_mode) {
     const int nb = (w_hi - w_lo + kW - 1) / kW;
     if (nb <= 0) return;
-    hipLaunchKernelGGL(k_lrf8, dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo, v.t3.hi,
-                       v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count);
+    if (seeded)
+        hipLaunchKernelGGL((k_lrf8<true, false>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
+    else if (seed != nullptr)
+        hipLaunchKernelGGL((k_lrf8<false, true>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
+    else
+        hipLaunchKernelGGL((k_lrf8<false, false>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
 }
 
 }  // namespace se3icp

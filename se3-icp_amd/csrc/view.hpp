@@ -139,8 +139,16 @@ void launch_lrf_list(const View& v, const int32_t* qlist, const int32_t* qcount,
 // aligned to each cloud); this launch runs waves w_lo .. w_hi-1; the queries it cannot
 // resolve exactly from f32 keys are appended to fb_list (count fb_count, zeroed by the
 // caller) for launch_lrf_list
+// Seeding (graph.hpp, graph_plan_seeds): seed[c] says where cloud c's waves store the f32 key
+// of each query's Kw-th neighbour (store, an offset into seedbuf indexed by local point; -1:
+// nowhere) or where they read the key a sibling class stored (load; -1: unseeded) and the
+// factor rho2 = (own scale / the sibling's)^2 that carries it over.  A launch is either of
+// storing and unseeded clouds (seeded = 0; seed may be null) or of seeded clouds only.
+// seed_mode: se3icp_set_lrf_seeding's 0, 2 (seeds halved) or 3 (seeds times 4).
+struct SeedRef { int32_t store; int32_t load; double rho2; };
 void launch_lrf8(const View& v, const int32_t* wave_base, int w_lo, int w_hi, int32_t* fb_list, int32_t* fb_count,
-                 hipStream_t s);
+                 hipStream_t s, const SeedRef* seed = nullptr, float* seedbuf = nullptr, bool seeded = false,
+                 int seed_mode = 0);
 // neighbourhoods over kSmallK (k_knn_big.hip): one wavefront per query with a global-memory
 // candidate buffer of `cap` entries per block; queries with Kw = min(k, n) <= k_min are
 // skipped (the LDS kernels'); qlist = nullptr: every point

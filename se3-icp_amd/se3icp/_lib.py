@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_register_sweep", "se3icp_register_sweep_device",
     "se3icp_register_graph", "se3icp_register_graph_device", "se3icp_register_graph_report",
     "se3icp_register_graph_report_device", "se3icp_last_graph_stats", "se3icp_set_batch_sharing",
+    "se3icp_set_lrf_seeding", "se3icp_last_seed_stats",
     "se3icp_report_version", "se3icp_register_batch_report", "se3icp_register_batch_report_device",
     "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
     "se3icp_request_report", "se3icp_get_report",
@@ -134,6 +135,8 @@ class Trace(C.Structure):
 # se3icp_last_graph_stats
 GRAPH_STATS = ["clouds", "uses", "classes", "classes_full", "adopted", "rejected_order", "rejected_gap", "no_list",
                "bytes_uploaded"]
+# se3icp_last_seed_stats
+SEED_STATS = ["classes_seeded", "queries_seeded", "queries_unseeded", "queries_failed"]
 
 
 class Se3IcpError(RuntimeError):
@@ -224,8 +227,9 @@ def load():
     L.se3icp_set_trace.argtypes = [C.c_int, C.POINTER(Trace)]
     L.se3icp_set_lrf_exact.argtypes = [C.c_int, C.c_int]
     L.se3icp_set_nn_events.argtypes = [C.c_int, C.c_int]
-    # (se3icp_set_batch_sharing(int, int) is called with ctypes' default int conversion and
-    # resolved at its first call: SE3ICP_LIB may name an older build for an A/B run)
+    # (se3icp_set_batch_sharing(int, int), se3icp_set_lrf_seeding(int, int) and
+    # se3icp_last_seed_stats(int, int64_t*, int) are called with ctypes' default conversions and
+    # resolved at their first call: SE3ICP_LIB may name an older build for an A/B run)
     _lib = L
     return L
 

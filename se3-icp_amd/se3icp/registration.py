@@ -773,6 +773,22 @@ def nearest_neighbors(query, data, device: int = 0):
     return idx, d2, int(nr.value)
 
 
+def set_lrf_seeding(mode: int, device: int = 0) -> None:
+    """How the classes of one cloud seed each other's neighbour selection on the engine behind
+    `device` (se3icp_set_lrf_seeding): 0 a cloud's later classes start from its first class's
+    neighbour distances (the default), 1 off, 2 / 3 diagnostics (every seed halved: the
+    certificate fails; every seed times 4: loose seeds).  Results are bitwise the same in every
+    mode; last_seed_stats() describes the last call."""
+    _lib.check(_lib.load().se3icp_set_lrf_seeding(int(device), int(mode)), "set_lrf_seeding")
+
+
+def last_seed_stats(device: int = 0) -> dict:
+    """Seeding counters of the last registration call on `device` (se3icp_last_seed_stats)."""
+    out = (C.c_int64 * len(_lib.SEED_STATS))()
+    _lib.check(_lib.load().se3icp_last_seed_stats(int(device), out, len(_lib.SEED_STATS)), "last_seed_stats")
+    return {k: int(out[i]) for i, k in enumerate(_lib.SEED_STATS)}
+
+
 def set_lrf_exact(mode, device: int = 0) -> None:
     """Diagnostic: which kernels compute the setup's kNN / TOLDI / normals.  0 / False: the
     default (k_lrf8 + hand-overs); 1 / True: the exact one-query-per-wavefront kernel for every

@@ -306,6 +306,25 @@ int se3icp_set_lrf_seeding(int device, int mode);
 #define SE3ICP_SEED_STATS_N 4
 int se3icp_last_seed_stats(int device, int64_t* out, int n);
 
+/* One kd-tree order per cloud.  The trees are implicit and balanced, their node ranges come
+ * from the point count alone and every search prunes on boxes computed from the points that
+ * are in a node, so any order with correct boxes is a valid tree and no result depends on it.
+ * Where several slots hold one confirmed cloud (se3icp_register_graph at sharing >= 2, a device
+ * batch that found a shared cloud) only the cloud's first slot builds its 3-D and 12-D trees;
+ * the later slots, of whatever class, take its finished order and compute their own
+ * tree-ordered vectors and boxes from their own coordinates.  Results are bitwise the same.
+ * mode: 0 adopt (the default of every engine), 1 off: every slot builds its own trees.
+ * Anything else is SE3ICP_ERR_INVALID_ARG, checked before the device is looked up.  The setting
+ * is the engine's (device | slot << 8) and does not depend on se3icp_set_lrf_seeding.  The
+ * host-pointer batch entries, the sweeps, batch sharing level 1 and graph sharing level 1 adopt
+ * nothing. */
+int se3icp_set_tree_sharing(int device, int mode);
+/* Of the last registration call on `device`: out[SE3ICP_TREE_STATS_N], n >= that (else
+ * SE3ICP_ERR_INVALID_ARG) = {3-D trees built, 3-D trees adopted, 12-D trees built, 12-D trees
+ * adopted}. */
+#define SE3ICP_TREE_STATS_N 4
+int se3icp_last_tree_stats(int device, int64_t* out, int n);
+
 /* ------------------------------------------------------------- registration reports
  * What says whether a pose is any good, evaluated at the FINAL pose as Open3D's
  * RegistrationResult and GetInformationMatrixFromPointClouds are.  For every source point i

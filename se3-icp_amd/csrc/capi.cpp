@@ -392,6 +392,24 @@ int se3icp_last_seed_stats(int device, int64_t* out, int n) {
     return SE3ICP_OK;
 }
 
+int se3icp_set_tree_sharing(int device, int mode) {
+    if (mode < se3icp::kTreeSharingMin || mode > se3icp::kTreeSharingMax) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_tree_sharing(mode);
+    return SE3ICP_OK;
+}
+
+int se3icp_last_tree_stats(int device, int64_t* out, int n) {
+    if (!out || n < 4) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    for (int k = 0; k < 4; ++k) out[k] = e->tree_stats()[k];
+    return SE3ICP_OK;
+}
+
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,
                     int method, const se3icp_params* params, se3icp_result* result) {
     return se3icp_register_batch(device, 1, &src_xyz, &n_src, &tgt_xyz, &n_tgt, method, params, result);

@@ -295,7 +295,8 @@ View Engine::view() const {
 }
 
 // ----------------------------------------------------------------------------- kd-trees
-int Engine::build_tree(int D, const float* vec, hipStream_t s, const double* vec64) {
+int Engine::build_tree(int D, const float* vec, hipStream_t s, const double* vec64, const std::vector<int32_t>* role,
+                       TreeTab* tab) {
     TreeBufs& tb = (D == 12) ? t12_ : t3_;
     tb.L = tree_L_;
     const int nnodes = 2 << tb.L;
@@ -335,6 +336,34 @@ int Engine::build_tree(int D, const float* vec, hipStream_t s, const double* vec
     t.scr = (float*)tb.scr.p;
     t.lo = (float*)tb.lo.p;
     t.hi = (float*)tb.hi.p;
+    // builders and adopters: with every cloud a builder the launches are those of a build
+    // without a table
+    int nbuild = nclouds_, nadopt = 0;
+    if (role && tab) {
+        nbuild = 0;
+        for (int c = 0; c < nclouds_; ++c) {
+            nbuild += (*role)[c] == kTreeBuilds;
+            nadopt += (*role)[c] >= 0;
+        }
+    }
+    if (nbuild != nclouds_) {
+        const size_t words = (size_t)nclouds_ + nbuild + nadopt;
+        if (tab->host.reserve(words) || !ensure<int32_t>(tab->dev, words)) return SE3ICP_ERR_OUT_OF_MEMORY;
+        int32_t* h = tab->host;
+        size_t at = (size_t)nclouds_;
+        for (int c = 0; c < nclouds_; ++c) h[c] = (*role)[c];
+        for (int c = 0; c < nclouds_; ++c)
+            if ((*role)[c] == kTreeBuilds) h[at++] = c;
+        for (int c = 0; c < nclouds_; ++c)
+            if ((*role)[c] >= 0) h[at++] = c;
+        HIPCHK(hipMemcpyAsync(tab->dev.p, h, sizeof(int32_t) * words, hipMemcpyHostToDevice, s));
+        t.role = (const int32_t*)tab->dev.p;
+        t.list = t.role + nclouds_;
+        t.nbuild = nbuild;
+        t.nadopt = nadopt;
+    }
+    tree_stats_[D == 12 ? 2 : 0] += nbuild;
+    tree_stats_[D == 12 ? 3 : 1] += nadopt;
     if (build_trees(t, d_sort_tmp_.p, d_sort_tmp_.bytes, (uint32_t*)d_keys0_.p, (int32_t*)d_vals1_.p, s) != 0)
         return SE3ICP_ERR_HIP;
     return 0;
@@ -611,6 +640,8 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     c->s = user_stream ? user_stream : stream_;
     ktimes_ = KernelTimes{};
     for (int64_t& x : seed_stats_) x = 0;
+    for (int64_t& x : tree_stats_) x = 0;
+    tree_donor_.clear();
     // phase times on the GPU timeline (the host does not wait for the setup): events
     // 12 (begin), 13 (setup done), 14 (loop done)
     HIPCHK(hipEventRecord(ev_[12], c->s));
@@ -624,7 +655,11 @@ int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const
     hipStream_t s = c.s;
     int rc = 0;
     // 12-D kd-trees over the alpha/beta-weighted SE(3) elements (f64 source elements in tree order)
-    if (mp.se3) rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p);
+    // (the later slots of a confirmed cloud adopt its first slot's order: graph_plan_trees)
+    const bool adopt12 = (int)tree_donor_.size() == nclouds_;
+    if (mp.se3)
+        rc = build_tree(12, (const float*)d_fr32_.p, s, (const double*)d_fr64_.p, adopt12 ? &tree_donor_ : nullptr,
+                        &tree_tab_12_);
     if (rc) return rc;
     rc = prepare_pairs(npairs, ns, nt, s);
     if (rc) return rc;
@@ -681,8 +716,10 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
 // ----------------------------------------------------------------------------- shared slots of a device batch
 // setup_clouds(clouds, on_device, pairs, normalize) for slots that may hold one cloud several
 // times (engine.hpp).  Every kernel setup_clouds queues is queued here, in its order and on its
-// tables, so a call without a confirmed duplicate is that path plus k_share_hash; the host
-// waits for the hashes while the device normalizes and builds the 3-D trees.
+// tables, so a call without a confirmed duplicate is that path plus k_share_hash.  With tree
+// sharing off the host waits for the hashes while the device normalizes and builds the 3-D
+// trees; with it (the default) the trees are queued in two parts around the compare flags, see
+// below.
 int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const MethodPlan& mp, double scale_pre,
                                hipStream_t s) {
     const int U = (int)clouds.size();
@@ -729,8 +766,16 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
     }
     launch_normalize(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
     HIPCHK(hipGetLastError());
-    rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
-    if (rc) return rc;
+    // The 3-D trees.  With tree sharing the later slots of a confirmed cloud adopt its first
+    // slot's order, and which slots those are is known only behind the compare flags: the slots
+    // that are no candidates build behind k_share_compare, so the device works through both
+    // host waits (the normalization is still queued behind the first), and the candidates
+    // follow the flags.  Without it every slot builds here, ahead of the first wait.
+    const bool adopt = tree_sharing_ != 1;
+    if (!adopt) {
+        rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+        if (rc) return rc;
+    }
     if (se3) HIPCHK(spin_wait(ev_[10]));
 
     // ---- candidates by (n, hash), confirmed byte for byte
@@ -749,8 +794,26 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_share_same_, d_share_same_.p, sizeof(int32_t) * U, hipMemcpyDeviceToHost, s));
         HIPCHK(hipEventRecord(ev_[11], s));
+        std::vector<int32_t> role(U);
+        if (adopt) {
+            for (int u = 0; u < U; ++u) role[u] = first[u] == u ? kTreeBuilds : kTreeAbsent;
+            rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p, &role, &tree_tab_a_);
+            if (rc) return rc;
+        }
         HIPCHK(spin_wait(ev_[11]));
         nc = share_clouds(U, first.data(), h_share_same_, &cloud);
+        if (adopt) {
+            // a confirmed slot adopts; a hash-equal slot the compare rejected builds
+            std::vector<int32_t> donor;
+            const int nad = graph_plan_trees(U, cloud.data(), n.data(), true, &donor);
+            for (int u = 0; u < U; ++u) role[u] = first[u] == u ? kTreeAbsent : donor[u];
+            rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p, &role, &tree_tab_b_);
+            if (rc) return rc;
+            if (nad > 0) tree_donor_ = donor;
+        }
+    } else if (adopt) {
+        rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+        if (rc) return rc;
     }
     if (nc == U) return setup_knn(s);  // every slot a cloud of its own: the batch's path
 
@@ -1592,7 +1655,19 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
     launch_graph_normalize(view(), (const ChunkWork*)d_chunks_.p, nchU2, (const GraphSeg*)g_seg_.p,
                            (const double*)g_raw_xyz_.p, (const double*)g_raw_conf_.p, s);
     HIPCHK(hipGetLastError());
-    rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
+    // the later uses of a cloud adopt its first use's tree order (graph_plan_trees)
+    {
+        std::vector<int32_t> ucloud(2 * (size_t)P), donor;
+        std::vector<int64_t> un(2 * (size_t)P);
+        for (int u = 0; u < 2 * P; ++u) {
+            ucloud[u] = plan.classes[plan.use_class[u]].cloud;
+            un[u] = clU[u].n;
+        }
+        const int nad = graph_plan_trees(2 * P, ucloud.data(), un.data(), sharing >= 2 && tree_sharing_ != 1, &donor);
+        if (nad > 0) tree_donor_ = donor;
+        rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p, nad > 0 ? &tree_donor_ : nullptr,
+                        &tree_tab_a_);
+    }
     if (rc) return rc;
     rc = select_by_class(plan, stU, mp, s);
     if (rc) return rc;

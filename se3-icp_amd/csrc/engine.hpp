@@ -89,6 +89,7 @@ class Engine {
     void set_nn_events(bool on) { nn_events_ = on; }
     void set_batch_sharing(int level) { batch_sharing_ = level; }
     void set_lrf_seeding(int mode) { lrf_seeding_ = mode; }
+    void set_tree_sharing(int mode) { tree_sharing_ = mode; }
     const KernelTimes& kernel_times() const { return ktimes_; }
 
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
@@ -117,6 +118,9 @@ class Engine {
     // waves that started from a seed, that ran without one, that were handed over after a
     // failed certificate
     const int64_t* seed_stats() const { return seed_stats_; }
+    // [4] of the last registration call (se3icp_last_tree_stats): 3-D trees built / adopted,
+    // 12-D trees built / adopted
+    const int64_t* tree_stats() const { return tree_stats_; }
 
     // stage entry points (host buffers)
     int knn_self(const double* xyz, int64_t n, int k, int32_t* idx);
@@ -141,8 +145,17 @@ class Engine {
     template <class T>
     T* ensure(DevBuf& b, size_t count);
     int alloc_points(int64_t ntot, int kmax, bool knn_list = false);
-    // build the D-dimensional kd-trees of every cloud over `vec` ([D][ld] f32)
-    int build_tree(int D, const float* vec, hipStream_t s, const double* vec64 = nullptr);
+    // build the D-dimensional kd-trees of every cloud over `vec` ([D][ld] f32).  role (null:
+    // every cloud builds) says per cloud kTreeBuilds, kTreeAbsent or the cloud whose finished
+    // order it adopts (tree.hpp); tab is the table's home on the host and the device until the
+    // call's last synchronisation.
+    struct TreeTab {
+        Pinned<int32_t> host;  // role [nclouds], then the builders' and the adopters' ids (pinned: an async copy)
+        DevBuf dev;
+        TreeTab(std::vector<PinnedMem*>& p, std::vector<DevBuf*>& o) : host(p), dev(o) {}
+    };
+    int build_tree(int D, const float* vec, hipStream_t s, const double* vec64 = nullptr,
+                   const std::vector<int32_t>* role = nullptr, TreeTab* tab = nullptr);
     // A registration call (register_batch, each group of register_sweep, register_graph) is
     // open_call, the entry's own setup of its clouds, and run_pairs.
     //
@@ -173,7 +186,8 @@ class Engine {
     // several times (graph.hpp): the slots are ingested, normalized and given their 3-D trees
     // in place exactly as setup_clouds does, hashed on the way, and compared where the hashes
     // agree; with a confirmed duplicate the neighbour selection runs once per class
-    // (select_by_class), otherwise as setup_knn.  Two host waits where setup_clouds has none
+    // (select_by_class), otherwise as setup_knn; with tree sharing the later slots of a confirmed
+    // cloud adopt its first slot's 3-D tree order (and, in run_pairs, its 12-D one).  Two host waits where setup_clouds has none
     // (run_se3_*) or one (vanilla): the hashes, with the normalization parameters the class
     // plan needs; the compare flags, only when some hash agreed.
     int setup_pairs_shared(const std::vector<CloudReq>& clouds, const MethodPlan& mp, double scale_pre, hipStream_t s);
@@ -237,6 +251,9 @@ class Engine {
     // se3icp_set_lrf_seeding: 0 a cloud's later classes start their selection from its first
     // class's neighbour distances (default), 1 off, 2 / 3 diagnostics: every seed halved / times 4
     int lrf_seeding_ = 0;
+    // se3icp_set_tree_sharing: 0 the later slots of a confirmed cloud adopt its first slot's tree
+    // order (default), 1 off
+    int tree_sharing_ = 0;
     se3icp_trace* trace_ = nullptr;      // armed per-iteration record of one pair (se3icp_set_trace)
     int record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t s);
     double trace_prev_[kStatCols] = {};
@@ -289,6 +306,13 @@ class Engine {
     int64_t seed_floats_ = 0;
     DevBuf d_seed_{bufs_}, d_seed_ref_{bufs_};
     int64_t seed_stats_[4] = {};
+    // graph_plan_trees of the call: per slot -1 or the slot whose tree order it adopts.  Set by
+    // setup_pairs_shared and register_graph, read by run_pairs for the 12-D trees, cleared by
+    // open_call (a call that shares nothing has no donors).  The tables of the call's builds:
+    // the 3-D trees queued before and behind the compare flags, the 12-D trees.
+    std::vector<int32_t> tree_donor_;
+    TreeTab tree_tab_a_{pins_, bufs_}, tree_tab_b_{pins_, bufs_}, tree_tab_12_{pins_, bufs_};
+    int64_t tree_stats_[4] = {};
     Pinned<PairDev> h_pairs_{pins_};
     Pinned<double> h_red_{pins_}, h_partial_{pins_};
     Pinned<int32_t> h_rechecked_{pins_};

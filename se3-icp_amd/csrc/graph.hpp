@@ -185,6 +185,39 @@ inline int32_t graph_plan_seeds(const GraphPlan& plan, const int32_t* k_knn, con
     return seeded;
 }
 
+// ---- one kd-tree order per cloud (build_trees, k_tree.hip)
+// The trees are implicit and balanced: node ranges come from the point count alone, every search
+// prunes on boxes computed from the points actually in a node, and no result depends on the
+// order.  So the later slots of a cloud take the order its first slot built and
+// compute only their own tree-ordered vectors and boxes.
+// se3icp_set_tree_sharing
+constexpr int kTreeSharingMin = 0, kTreeSharingMax = 1;
+// cloud [n_slots]: the confirmed cloud of every slot (byte-compared in a device batch, named by
+// the caller in a graph), or negative for a slot nothing is known about; n_pts [n_slots].
+// donor[u]: -1 where slot u builds its trees, otherwise the first slot of its cloud, whose
+// order it adopts -- whatever its class.  A slot adopts only from a slot of the same cloud and
+// point count.  share = false (sharing level 1, tree sharing off): every slot builds.  The
+// table serves the 3-D trees, and the 12-D trees of a method with an SE(3) phase.  Returns the
+// adopters.
+inline int32_t graph_plan_trees(int32_t n_slots, const int32_t* cloud, const int64_t* n_pts, bool share,
+                                std::vector<int32_t>* donor) {
+    donor->assign((size_t)n_slots, -1);
+    if (!share) return 0;
+    std::map<int32_t, int32_t> first;  // cloud -> its first slot
+    int32_t adopters = 0;
+    for (int32_t u = 0; u < n_slots; ++u) {
+        if (cloud[u] < 0) continue;
+        auto it = first.find(cloud[u]);
+        if (it == first.end()) {
+            first[cloud[u]] = u;
+        } else if (n_pts[it->second] == n_pts[u]) {
+            (*donor)[u] = it->second;
+            ++adopters;
+        }
+    }
+    return adopters;
+}
+
 // Plan the classes of P edges over clouds the caller names.
 //   normalize: centre on the own centroid, scale by the pair; otherwise the f32 copy is centred
 //              on the edge's target.

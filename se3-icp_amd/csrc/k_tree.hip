@@ -17,6 +17,10 @@
 //     leaves and inner nodes; k_tree_up unions the boxes above.
 //   At C4 (16 clouds of ~120k points): 17 launches for the 3-D tree, 25 for the 12-D one.
 //   Leaves hold <= 64 points.
+//   * a cloud that holds the points of an earlier one (TreeView::role) builds nothing: node
+//     ranges come from the point count alone and every search prunes on the boxes, so it takes
+//     the earlier cloud's final permutation and one more k_tree_local launch (ADOPT) writes its
+//     own tree-ordered vectors and boxes; the builders' launches are those of a build without it.
 // Outputs per cloud: perm (tree position -> point), pos (inverse), the vectors in tree
 // order (coalesced leaf loads) and f32 AABBs of all 2^(L+1)-1 nodes (heap order),
 // inflated by a few ulps so the f32 boxes bound the f64 points they stand for.
@@ -53,7 +57,7 @@ __device__ __forceinline__ float ord_float(uint32_t u) {
 // cleared
 __global__ __launch_bounds__(256) void k_tree_init(TreeView t, int32_t* perm2, int box_nodes) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < t.npts) {
+    if (g < t.npts && tree_builds(t, t.cloud_of[g])) {  // (an adopter's order is written by its adopt launch)
         const CloudDev cl = t.clouds[t.cloud_of[g]];
         t.perm[g] = g - cl.off;
         perm2[g] = g - cl.off;  // (both buffers hold valid point indices at all times)
@@ -86,7 +90,9 @@ template <int D>
 __global__ __launch_bounds__(256) void k_tree_bbox(TreeView t, int level) {
     const int g = (blockIdx.x * blockDim.x + threadIdx.x) * kSplitSample;
     const int lane = threadIdx.x & 63;
-    const bool valid = g < t.npts;
+    // (with adopters a block may begin among skipped samples: its valid ones then take the
+    // global atomics below, k0 < 0)
+    const bool valid = g < t.npts && tree_builds(t, t.cloud_of[g]);
     int c = -1, node = -1;
     uint32_t lo[D], hi[D];
     if (valid) {
@@ -233,10 +239,10 @@ __device__ __forceinline__ PartDim part_dim_of(const uint32_t* blo, const uint32
 // every node's split from its sampled box (k_tree_bbox); once per node, not per point
 __global__ __launch_bounds__(64) void k_part_dims(TreeView t, int level, PartDim* dims) {
     const int id = blockIdx.x * 64 + threadIdx.x;
-    if (id >= (t.nclouds << level)) return;
-    const int c = id >> level, node = id & ((1 << level) - 1);
+    if (id >= ((t.list ? t.nbuild : t.nclouds) << level)) return;
+    const int c = tree_list_cloud(t, id >> level), node = id & ((1 << level) - 1);
     const size_t base = ((size_t)c * t.nnodes + tree_heap(level, node)) * t.D;
-    dims[id] = part_dim_of(t.blo + base, t.bhi + base, t.D);
+    dims[(c << level) + node] = part_dim_of(t.blo + base, t.bhi + base, t.D);
 }
 
 // node ids (cloud << level | node) grow with the tree position
@@ -261,7 +267,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part_hist(TreeView t, int leve
 #pragma unroll 4
     for (int u = 0; u < kHistPer; ++u) {
         const int g = g0 + u * kPartThreads + tid;
-        if (g < t.npts) {
+        if (g < t.npts && tree_builds(t, t.cloud_of[g])) {
             const int c = t.cloud_of[g];
             const CloudDev cl = t.clouds[c];
             const int node = tree_node_of(g - cl.off, cl.n, level);
@@ -291,8 +297,8 @@ __global__ __launch_bounds__(kPartThreads) void k_part_hist(TreeView t, int leve
 __global__ __launch_bounds__(kSelThreads) void k_part_select(TreeView t, int level, uint32_t* overflow, PartSel* sel) {
     __shared__ uint32_t s_sum[kSelThreads];
     const int nl = 1 << level;
-    const int id = blockIdx.x;
-    const int c = id >> level, node = id & (nl - 1);
+    const int c = tree_list_cloud(t, blockIdx.x >> level), node = blockIdx.x & (nl - 1);
+    const int id = part_node_id(c, level, node);
     const CloudDev cl = t.clouds[c];
     const int a = tree_first(cl.n, level, node);
     const int mL = tree_first(cl.n, level + 1, 2 * node + 1) - a;
@@ -336,17 +342,18 @@ __global__ __launch_bounds__(kSelThreads) void k_part_select(TreeView t, int lev
 __global__ __launch_bounds__(256) void k_part_hist2(TreeView t, int level, const uint32_t* key, const PartSel* sel,
                                                    uint32_t* fine) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= t.npts) return;
+    if (g >= t.npts || !tree_builds(t, t.cloud_of[g])) return;
     const int id = part_node_id_at(t, level, g);
     const uint32_t k = key[g];
     if ((int)(k >> kPartBits) == sel[id].bin) atomicAdd(&fine[(size_t)id * kPartBins + (k & (kPartBins - 1))], 1u);
 }
 
 // the fine bin holding the median position; sel becomes the full-key threshold
-__global__ __launch_bounds__(256) void k_part_select2(uint32_t* fine, PartSel* sel) {
+__global__ __launch_bounds__(256) void k_part_select2(TreeView t, int level, uint32_t* fine, PartSel* sel) {
     __shared__ uint32_t s_sum[256];
     constexpr int kPer = kPartBins / 256;
-    const int id = blockIdx.x, tid = threadIdx.x;
+    const int id = part_node_id(tree_list_cloud(t, blockIdx.x >> level), level, blockIdx.x & ((1 << level) - 1));
+    const int tid = threadIdx.x;
     const PartSel r = sel[id];
     const int want = r.tie_left;  // points of the coarse bin that go left
     uint32_t* h = fine + (size_t)id * kPartBins;
@@ -437,7 +444,8 @@ __global__ __launch_bounds__(kPartThreads) void k_part_count(TreeView t, int lev
 #pragma unroll
     for (int u = 0; u < kPartPer; ++u) {
         const int g = g0 + u;
-        if (g < t.npts) {
+        // (a skipped point adds nothing: the next builder's node starts with its own flag)
+        if (g < t.npts && tree_builds(t, t.cloud_of[g])) {
             int k, node, c;
             acc = seg_add(acc, part_class(t, level, q, sel, g, &k, &node, &c));
         }
@@ -483,8 +491,8 @@ __global__ __launch_bounds__(kPartThreads) void k_part_scatter(TreeView t, int l
         self[u] = SegCnt{0ull, 0};
         cls[u] = 2;
         nodes[u] = 0;
-        cs[u] = 0;
-        if (g < t.npts) self[u] = part_class(t, level, q, sel, g, &cls[u], &nodes[u], &cs[u]);
+        cs[u] = -1;  // (stays -1 for a point past the end or of a cloud that does not build)
+        if (g < t.npts && tree_builds(t, t.cloud_of[g])) self[u] = part_class(t, level, q, sel, g, &cls[u], &nodes[u], &cs[u]);
         acc = seg_add(acc, self[u]);
     }
     SegCnt ex;
@@ -496,7 +504,7 @@ __global__ __launch_bounds__(kPartThreads) void k_part_scatter(TreeView t, int l
     for (int u = 0; u < kPartPer; ++u) {
         const int g = g0 + u;
         if (self[u].f) run = SegCnt{0ull, 0};
-        if (g < t.npts) {
+        if (cs[u] >= 0) {
             const CloudDev cl = t.clouds[cs[u]];
             const int a = tree_first(cl.n, level, nodes[u]);
             const int mL = tree_first(cl.n, level + 1, 2 * nodes[u] + 1) - a;
@@ -581,7 +589,7 @@ __global__ __launch_bounds__(kLevThreads) void k_tree_level(TreeView t, int leve
     __shared__ uint32_t s_w[kLevWaves];
     __shared__ int s_sel[3];
     __shared__ uint32_t s_cnt[kLevWaves][2];
-    const int c = blockIdx.x >> level, node = blockIdx.x & ((1 << level) - 1);
+    const int c = tree_list_cloud(t, blockIdx.x >> level), node = blockIdx.x & ((1 << level) - 1);
     const CloudDev cl = t.clouds[c];
     const int n = cl.n;
     const int a = tree_first(n, level, node), m = tree_first(n, level, node + 1) - a;
@@ -780,7 +788,12 @@ __global__ __launch_bounds__(kLevThreads) void k_tree_level(TreeView t, int leve
 constexpr int kLocalThreads = 512;
 static_assert(kLocalSubsMax <= 128, "s_best / s_mu / s_sd hold one entry per sub-node");
 
-template <int D>
+// ADOPT: the launch for the clouds that take another cloud's order (TreeView::role).  The
+// donor's final permutation segment of the same level-G node stands in for the load and the
+// levels -- equal point counts give equal node ranges -- and the final and box phases run as
+// written, on the adopter's own vectors.  The donor's k_tree_local has finished: this is a
+// later launch on the stream.
+template <int D, bool ADOPT>
 // (4 waves per SIMD: two workgroups per CU, <= 128 VGPRs)
 __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_tree_local(TreeView t, int G) {
     __shared__ unsigned long long s_key[kLocalMax];  // (histograms, then one column of the node)
@@ -796,12 +809,17 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
     __shared__ float s_smp[D][kSmp];
     __shared__ int32_t s_spos[kSmp];
     const int nG = 1 << G;
-    const int c = blockIdx.x / nG, i = blockIdx.x % nG;
+    const int c = tree_list_cloud(t, (ADOPT ? t.nbuild : 0) + blockIdx.x / nG), i = blockIdx.x % nG;
     const CloudDev cl = t.clouds[c];
     const int n = cl.n;
     const int A = tree_first(n, G, i), m = tree_first(n, G, i + 1) - A;
     const int tid = threadIdx.x;
     const size_t ld = t.ld;
+    // (ADOPT) the donor's order of this node: local point indices, valid for the adopter's points
+    const int32_t* const dperm = ADOPT ? t.perm + t.clouds[t.role[c]].off + A : nullptr;
+    if constexpr (ADOPT) {
+        if (t.clouds[t.role[c]].n != n) return;  // (never, by the plan; block-uniform)
+    }
     // the node's vectors at the level-G positions, one column per dimension (col0[d * m + e]):
     // a level gathers one coordinate of every point, 4 B from a 16-KB column instead of a
     // 64-B sector of a 48-B row (round 3: 1.7 GB of HBM traffic per 12-D launch)
@@ -814,6 +832,7 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
     // of the thread first, then the rows in batches of LB with all their loads issued before
     // the column stores (a load after a store to another global array is not hoisted above
     // it, so one point at a time was two dependent round trips per point)
+    if constexpr (!ADOPT) {  // ---- load and levels: builders only (down to the final order below)
     {
         constexpr int LP = kLocalMax / kLocalThreads;
         constexpr int LB = D == 12 ? 4 : LP;
@@ -1156,6 +1175,7 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
         atomicAdd(&g_tree_lev[D == 12][8], 1ull);
     }
 #endif
+    }  // (!ADOPT)
     // the final order, a wave per leaf (<= 64 consecutive tree positions): permutation,
     // inverse, f32 and f64 vectors (the layouts k_tree_finish writes) and the leaf's box
     // (inflated as k_tree_leafbox does)
@@ -1187,7 +1207,8 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
             // lanes outside the leaf load nothing: for an empty node (m == 0) or a trailing
             // empty leaf s_val / s_p hold no point of this cloud, and cl.off + s_p[..] could
             // lie before the buffer
-            pq[b] = inq[b] ? s_p[s_val[xq[b]]] : 0;
+            if constexpr (ADOPT) pq[b] = inq[b] ? dperm[xq[b]] : 0;
+            else pq[b] = inq[b] ? s_p[s_val[xq[b]]] : 0;
             const int src = cl.off + pq[b];
 #pragma unroll
             for (int d = 0; d < D; ++d) v[b][d] = 0.0f;
@@ -1282,7 +1303,7 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
     }
 #ifdef SE3ICP_PROF
     tq[4] = __builtin_amdgcn_s_memrealtime();
-    if (tid == 0) {
+    if (!ADOPT && tid == 0) {  // (the phase timeline is the builders')
         atomicMin(&g_tree_prof[D == 12][0], tq[0]);
         for (int k = 1; k < 5; ++k) atomicMax(&g_tree_prof[D == 12][k], tq[k]);
     }
@@ -1291,9 +1312,18 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
 
 __global__ __launch_bounds__(256) void k_tree_finish(TreeView t) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g < t.npts) {
+    const int role = (g < t.npts && t.role) ? t.role[t.cloud_of[g]] : kTreeBuilds;
+    if (g < t.npts && role != kTreeAbsent) {
         const CloudDev cl = t.clouds[t.cloud_of[g]];
-        const int p = t.perm[g];
+        int p = t.perm[g];
+        if (role >= 0) {
+            // an adopter: its donor's order (a builder of this or an earlier build, whose
+            // permutation no thread of this launch writes); equal point counts, by the plan
+            const CloudDev dl = t.clouds[role];
+            if (dl.n != cl.n) return;
+            p = t.perm[dl.off + (g - cl.off)];
+            t.perm[g] = p;
+        }
         const int src = cl.off + p;
         t.pos[src] = g - cl.off;
         const bool want64 = (t.tvec64 != nullptr) & !((t.vec64_sources_only != 0) & ((t.cloud_of[g] & 1) != 0));
@@ -1326,6 +1356,7 @@ __global__ __launch_bounds__(256) void k_tree_leafbox(TreeView t) {
     const int nleaf = 1 << t.L;
     if (w >= t.nclouds * nleaf) return;
     const int c = w / nleaf, i = w % nleaf;
+    if (t.role && t.role[c] == kTreeAbsent) return;
     const CloudDev cl = t.clouds[c];
     const int a = tree_first(cl.n, t.L, i), b = tree_first(cl.n, t.L, i + 1);
     const bool valid = lane < b - a;
@@ -1353,7 +1384,7 @@ __global__ __launch_bounds__(256) void k_tree_leafbox(TreeView t) {
 // internal boxes of the levels above `top` = unions of the children, level by level (one
 // block per cloud)
 __global__ __launch_bounds__(1024) void k_tree_up(TreeView t, int top) {
-    const int c = blockIdx.x;
+    const int c = tree_list_cloud(t, blockIdx.x);  // (builders and adopters of this build)
     // (a loop source cloud's 12-D tree has no boxes: see k_tree_local's order_only)
     if (SE3ICP_TREE_SRC_ORDER_ONLY && (t.D == 12) && (t.vec64_sources_only != 0) && ((c & 1) == 0)) return;
     for (int l = top - 1; l >= 0; --l) {
@@ -1419,6 +1450,11 @@ int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t
     int max_n = 0;
     for (int c = 0; c < t.nclouds; ++c) max_n = std::max(max_n, t.host_n[c]);
     const int G = tree_global_levels(max_n, t.L);
+    // builders and adopters (TreeView::role): the grids per node and the choice of H count the
+    // builders only, so they run the launches of a build without the other clouds; the kernels
+    // over all points skip the rest
+    if (!t.list) t.nbuild = t.nclouds, t.nadopt = 0;
+    const int ncb = t.nbuild, nca = t.nadopt;
     PartScratch ps;
     if (part_layout(t.npts, t.nclouds, G, (char*)tmp, &ps) > tmp_bytes) return -1;
     // the level scatters alternate between the two permutation buffers: start in the one
@@ -1431,15 +1467,17 @@ int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t
     // (12-D: a level of 32 nodes through the multi-pass sequence too -- one 1024-thread
     // workgroup per 60k-point node left 7/8 of the CUs idle for 120 us; 3-D breaks even)
     const int wg_min = t.D == 12 ? 2 * kTreeWgMin : kTreeWgMin;
-    while (H < G && (t.nclouds << H) < wg_min) ++H;
-    hipLaunchKernelGGL(k_tree_init, dim3(gfill), dim3(256), 0, s, tc, other, (1 << H) - 1);
-    if (ps.overflow_words) hipLaunchKernelGGL(k_clear_words, dim3(256), dim3(256), 0, s, ps.overflow, ps.overflow_words);
+    while (H < G && (ncb << H) < wg_min) ++H;
     const int nblk = (t.npts + kPartElems - 1) / kPartElems;
     const int nhist = (t.npts + kHistElems - 1) / kHistElems;
-    for (int l = 0; l < G; ++l) {
+    if (ncb > 0) {
+        hipLaunchKernelGGL(k_tree_init, dim3(gfill), dim3(256), 0, s, tc, other, (1 << H) - 1);
+        if (ps.overflow_words) hipLaunchKernelGGL(k_clear_words, dim3(256), dim3(256), 0, s, ps.overflow, ps.overflow_words);
+    }
+    for (int l = 0; l < G && ncb > 0; ++l) {
         if (l >= H) {
             // enough nodes to fill the GPU with a workgroup each: one launch for the level
-            hipLaunchKernelGGL(t.D == 12 ? k_tree_level<12> : k_tree_level<3>, dim3(t.nclouds << l), dim3(kLevThreads), 0,
+            hipLaunchKernelGGL(t.D == 12 ? k_tree_level<12> : k_tree_level<3>, dim3(ncb << l), dim3(kLevThreads), 0,
                                s, tc, l, (const int32_t*)tc.perm, other, qbuf);
             std::swap(tc.perm, other);
             continue;
@@ -1448,12 +1486,12 @@ int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t
         // (the split dimension from every kSplitSample-th point's box: estimating the
         // children's boxes from the parent's cut was measured to give slower searches)
         hipLaunchKernelGGL(bbox, dim3(nbs), dim3(256), 0, s, tc, l);
-        hipLaunchKernelGGL(k_part_dims, dim3(((t.nclouds << l) + 63) / 64), dim3(64), 0, s, tc, l, dims);
+        hipLaunchKernelGGL(k_part_dims, dim3(((ncb << l) + 63) / 64), dim3(64), 0, s, tc, l, dims);
         hipLaunchKernelGGL(k_part_hist, dim3(nhist), dim3(kPartThreads), 0, s, tc, l, dims, qbuf, ps.overflow);
-        hipLaunchKernelGGL(k_part_select, dim3(t.nclouds << l), dim3(kSelThreads), 0, s, tc, l, ps.overflow, ps.sel);
+        hipLaunchKernelGGL(k_part_select, dim3(ncb << l), dim3(kSelThreads), 0, s, tc, l, ps.overflow, ps.sel);
         hipLaunchKernelGGL(k_part_hist2, dim3(nb), dim3(256), 0, s, tc, l, (const uint32_t*)qbuf, (const PartSel*)ps.sel,
                            ps.overflow);
-        hipLaunchKernelGGL(k_part_select2, dim3(t.nclouds << l), dim3(256), 0, s, ps.overflow, ps.sel);
+        hipLaunchKernelGGL(k_part_select2, dim3(ncb << l), dim3(256), 0, s, tc, l, ps.overflow, ps.sel);
         hipLaunchKernelGGL(k_part_count, dim3(nblk), dim3(kPartThreads), 0, s, tc, l, (const uint32_t*)qbuf,
                            (const PartSel*)ps.sel, ps.tails);
         hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, s, (const SegCnt*)ps.tails, nblk, ps.carry);
@@ -1462,16 +1500,22 @@ int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t
         std::swap(tc.perm, other);
     }
     t.perm = final_perm;
+    if (ncb + nca == 0) return 0;
     if (G < t.L) {
-        // the levels below G, the tree-ordered vectors and the boxes below G per level-G node
-        hipLaunchKernelGGL(t.D == 12 ? k_tree_local<12> : k_tree_local<3>, dim3(t.nclouds << G), dim3(kLocalThreads), 0,
-                           s, t, G);
-        hipLaunchKernelGGL(k_tree_up, dim3(t.nclouds), dim3(1024), 0, s, t, G);
+        // the levels below G, the tree-ordered vectors and the boxes below G per level-G node;
+        // then the adopters, whose donors' final order is complete behind that launch (or was
+        // built by an earlier call)
+        auto local = t.D == 12 ? k_tree_local<12, false> : k_tree_local<3, false>;
+        auto adopt = t.D == 12 ? k_tree_local<12, true> : k_tree_local<3, true>;
+        if (ncb > 0) hipLaunchKernelGGL(local, dim3(ncb << G), dim3(kLocalThreads), 0, s, t, G);
+        if (nca > 0) hipLaunchKernelGGL(adopt, dim3(nca << G), dim3(kLocalThreads), 0, s, t, G);
+        hipLaunchKernelGGL(k_tree_up, dim3(ncb + nca), dim3(1024), 0, s, t, G);
     } else {
+        // (an adopter reads its donor's identity order here: no level has moved it)
         hipLaunchKernelGGL(k_tree_finish, dim3(nb), dim3(256), 0, s, t);
         const int nleaves = t.nclouds << t.L;
         hipLaunchKernelGGL(t.D == 12 ? k_tree_leafbox<12> : k_tree_leafbox<3>, dim3((nleaves + 3) / 4), dim3(256), 0, s, t);
-        hipLaunchKernelGGL(k_tree_up, dim3(t.nclouds), dim3(1024), 0, s, t, t.L);
+        hipLaunchKernelGGL(k_tree_up, dim3(ncb + nca), dim3(1024), 0, s, t, t.L);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

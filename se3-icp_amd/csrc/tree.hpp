@@ -41,7 +41,19 @@ struct TreeView {
     float* lo;         // [nclouds][nnodes][D] node boxes
     float* hi;
     const int32_t* host_n;  // host copy of the clouds' point counts (level split of the build)
+    // Builders and adopters of this build (graph.hpp, graph_plan_trees): a cloud that holds the
+    // points of an earlier one takes that cloud's finished order and computes only its own
+    // tree-ordered vectors and boxes.  All null / 0: every cloud builds.
+    const int32_t* role;  // [nclouds] kTreeBuilds, kTreeAbsent, or the cloud whose order it adopts
+    const int32_t* list;  // the builders' cloud ids (nbuild), then the adopters' (nadopt)
+    int32_t nbuild, nadopt;
 };
+constexpr int32_t kTreeBuilds = -1;  // builds its own tree
+constexpr int32_t kTreeAbsent = -2;  // takes no part in this build (its tree comes from another one)
+
+// cloud of the j-th builder / (j - nbuild)-th adopter
+__device__ __forceinline__ int tree_list_cloud(const TreeView& t, int j) { return t.list ? t.list[j] : j; }
+__device__ __forceinline__ bool tree_builds(const TreeView& t, int c) { return !t.role || t.role[c] == kTreeBuilds; }
 
 __host__ __device__ __forceinline__ int tree_first(int n, int level, int i) {
     return (int)(((long long)n * i) >> level);

@@ -17,7 +17,8 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            register_sweep_report_device,
                            expand_edges, last_graph_stats, register_graph, register_graph_device,
                            register_graph_report, register_graph_traced, register_sequence, sequence_edges,
-                           set_batch_sharing, set_lrf_seeding, last_seed_stats)
+                           set_batch_sharing, set_lrf_seeding, last_seed_stats,
+                           set_tree_sharing, last_tree_stats)
 from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
@@ -29,5 +30,5 @@ __all__ = [
     "register_sweep_report", "register_sweep_report_device",
     "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
     "register_graph_report", "register_graph_traced", "last_graph_stats",
-    "set_batch_sharing", "set_lrf_seeding", "last_seed_stats",
+    "set_batch_sharing", "set_lrf_seeding", "last_seed_stats", "set_tree_sharing", "last_tree_stats",
 ]

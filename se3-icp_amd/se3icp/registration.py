@@ -789,6 +789,21 @@ def last_seed_stats(device: int = 0) -> dict:
     return {k: int(out[i]) for i, k in enumerate(_lib.SEED_STATS)}
 
 
+def set_tree_sharing(mode: int, device: int = 0) -> None:
+    """Whether the later slots of a confirmed cloud take its first slot's kd-tree order on the
+    engine behind `device` (se3icp_set_tree_sharing): 0 adopt (the default), 1 off, every slot
+    builds its own trees.  Results are bitwise the same; last_tree_stats() describes the last
+    call."""
+    _lib.check(_lib.load().se3icp_set_tree_sharing(int(device), int(mode)), "set_tree_sharing")
+
+
+def last_tree_stats(device: int = 0) -> dict:
+    """Trees built and adopted by the last registration call on `device` (se3icp_last_tree_stats)."""
+    out = (C.c_int64 * len(_lib.TREE_STATS))()
+    _lib.check(_lib.load().se3icp_last_tree_stats(int(device), out, len(_lib.TREE_STATS)), "last_tree_stats")
+    return {k: int(out[i]) for i, k in enumerate(_lib.TREE_STATS)}
+
+
 def set_lrf_exact(mode, device: int = 0) -> None:
     """Diagnostic: which kernels compute the setup's kNN / TOLDI / normals.  0 / False: the
     default (k_lrf8 + hand-overs); 1 / True: the exact one-query-per-wavefront kernel for every

@@ -460,6 +460,48 @@ int64_t se3icp_synthetic_reference_device(int device, const double* cloud, int64
  * the kept points in file order into out [k * 3] (may be NULL); returns k. */
 int64_t se3icp_random_downsample(const double* xyz, int64_t n, double ratio, uint32_t seed, double* out);
 
+/* ------------------------------------------------------------- voxel-grid downsample
+ * What turns a raw scan into the cloud the reference's drivers register (their inputs are
+ * already downsampled; VoxelDownSample(0.0042) is the bunny drivers' commented alternative,
+ * examples/registration_example.cpp:17-18): Open3D PointCloud::VoxelDownSample for xyz, on the
+ * GPU, batched, from HBM into HBM.  All f64:
+ *   min_bound = min(p) - 0.5 * voxel_size                       per cloud and axis
+ *   cell(p)   = floor((p - min_bound) / voxel_size)             one subtraction, one division
+ *   output    = sum / (double)count, sum the sequential f64 sum of the cell's points in
+ *               input-index order (Open3D's AccumulatedPoint::AddPoint order, from +0.0)
+ * so a restatement that does the same IEEE operations gives the same bits.  Output order: Open3D's
+ * is its unordered_map's, i.e. unspecified; here it is FIRST OCCURRENCE -- voxels ascending by
+ * the lowest input index they contain -- whatever the batch around the cloud, the engine slot or
+ * the layout of the hash table that groups the points.
+ * Errors, the arguments checked before the device is looked up: SE3ICP_ERR_INVALID_ARG for
+ * n_clouds <= 0, a NULL array, a voxel_size <= 0 or not finite; SE3ICP_ERR_EMPTY_CLOUD for a
+ * cloud of 0 points; without a device SE3ICP_ERR_NO_DEVICE, never a CPU fallback.  Found on the
+ * device and returned at the call's end (no output is then to be used): SE3ICP_ERR_NONFINITE for
+ * a NaN or infinite coordinate; SE3ICP_ERR_INVALID_ARG for Open3D's "voxel_size is too small"
+ * (voxel_size * INT_MAX < the largest extent of [min_bound, max(p) + 0.5 * voxel_size]) and,
+ * A DEPARTURE FROM OPEN3D, for a grid whose three per-axis cell indices do not pack into one
+ * 63-bit key (bit lengths of the largest index per axis summing to more than 63: Open3D hashes
+ * an int triple and has no such bound); SE3ICP_ERR_INTERNAL if the grouping table ran full
+ * (it holds twice the points; every probe sequence is bounded by it).  More than 65,535 clouds
+ * or 2^30 points in one call: SE3ICP_ERR_INVALID_ARG. */
+int se3icp_voxel_version(void);  /* 1 */
+/* d_xyz: the device concatenation of every cloud's AoS xyz, off (n_clouds + 1 host entries)
+ * each cloud's point range, voxel_size (n_clouds host entries) each cloud's own.  d_out: device,
+ * room for off[n_clouds] - off[0] points; the clouds' outputs are written compacted and
+ * contiguous and out_off (n_clouds + 1 host entries, out_off[0] = 0) is filled, so (d_out, out_off)
+ * go straight into se3icp_register_batch_device / se3icp_register_graph_device.  d_count
+ * (points per output voxel) and d_first (its lowest input index, relative to the cloud): optional
+ * device outputs laid out as d_out's points, either may be NULL.  Kernels run on hip_stream
+ * (NULL = the engine's own stream); the call waits once, at its end, to read the counts. */
+int se3icp_voxel_downsample_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                   const double* voxel_size, double* d_out, int64_t* out_off, int32_t* d_count,
+                                   int32_t* d_first, void* hip_stream);
+/* One host cloud: out [n * 3], count [n], first [n] host arrays with room for n entries (any may
+ * be NULL; all NULL returns the size only).  Returns the number of output points or a negative
+ * se3icp_status. */
+int64_t se3icp_voxel_downsample(int device, const double* xyz, int64_t n, double voxel_size, double* out,
+                                int32_t* count, int32_t* first);
+
 /* ------------------------------------------------------------- diagnostics
  * Not part of the reference boundary: per-kernel GPU times (HIP events) of the
  * last batch on `device`, used by bench.py for the roofline figures.

@@ -570,6 +570,38 @@ int se3icp_nn(int device, const double* query, int64_t nq, const double* data, i
     return e->nn(query, nq, data, nd, dim, idx, d2, num_rechecked);
 }
 
+// ------------------------------------------------------------------ voxel-grid downsample
+// Arguments are checked before the device is looked up, as the sweeps' are (voxel.hpp).
+int se3icp_voxel_version(void) { return 1; }
+
+int se3icp_voxel_downsample_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                   const double* voxel_size, double* d_out, int64_t* out_off, int32_t* d_count,
+                                   int32_t* d_first, void* hip_stream) {
+    const int rc = se3icp::voxel_check_sizes(n_clouds, off, voxel_size, SE3ICP_ERR_INVALID_ARG, SE3ICP_ERR_EMPTY_CLOUD);
+    if (rc) return rc;
+    if (!d_xyz || !d_out || !out_off) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->voxel_downsample(n_clouds, d_xyz, off, voxel_size, d_out, out_off, d_count, d_first,
+                               (hipStream_t)hip_stream);
+}
+
+int64_t se3icp_voxel_downsample(int device, const double* xyz, int64_t n, double voxel_size, double* out,
+                                int32_t* count, int32_t* first) {
+    const int64_t off[2] = {0, n};
+    if (n < 0) return SE3ICP_ERR_INVALID_ARG;
+    const int rc = se3icp::voxel_check_sizes(1, off, &voxel_size, SE3ICP_ERR_INVALID_ARG, SE3ICP_ERR_EMPTY_CLOUD);
+    if (rc) return rc;
+    if (!xyz) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    int64_t n_out = 0;
+    const int rc2 = e->voxel_downsample_host(xyz, n, voxel_size, out, count, first, &n_out);
+    return rc2 ? rc2 : n_out;
+}
+
 // ------------------------------------------------------------------ profiling hooks (not part of the
 // reference boundary; used by bench.py to read the per-kernel HIP-event times of the last batch)
 int se3icp_set_profiling(int device, int on) {

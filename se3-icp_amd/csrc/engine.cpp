@@ -1906,6 +1906,104 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
 }
 
 // ----------------------------------------------------------------------------- engine registry
+// ----------------------------------------------------------------------------- voxel-grid downsample
+int Engine::voxel_downsample(int nclouds, const double* d_xyz, const int64_t* off, const double* vs, double* d_out,
+                             int64_t* out_off, int32_t* d_count, int32_t* d_first, hipStream_t user_stream) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    if (!d_xyz || !d_out || !out_off) return SE3ICP_ERR_INVALID_ARG;
+    if (nclouds > 65535) return SE3ICP_ERR_INVALID_ARG;  // one grid row per cloud
+    HIPCHK(hipSetDevice(dev_));
+    hipStream_t s = user_stream ? user_stream : stream_;
+    if (h_vclouds_.reserve(nclouds)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    int64_t N = 0, slots = 0, chunks = 0;
+    int max_chunks = 1;
+    for (int c = 0; c < nclouds; ++c) {
+        const int64_t n = off[c + 1] - off[c];
+        if (N + n >= (int64_t)1 << 30) return SE3ICP_ERR_INVALID_ARG;  // as a batch's points
+        VoxelCloud& cl = h_vclouds_[c];
+        cl.off = off[c];
+        cl.pt0 = N;
+        cl.tab = slots;
+        cl.slots = voxel_table_slots(n);
+        cl.chunk0 = chunks;
+        cl.voxel_size = vs[c];
+        cl.n = (int32_t)n;
+        cl.nchunks = (int32_t)((n + kVoxChunkPoints - 1) / kVoxChunkPoints);
+        N += n;
+        slots += cl.slots;
+        chunks += cl.nchunks;
+        max_chunks = std::max(max_chunks, (int)cl.nchunks);
+    }
+    const int64_t big_cap = N / (kVoxLane + 1) + 1;
+    const size_t nflags = 2 * (size_t)nclouds + 2;  // status, n_out, error, n_big
+    VoxelArgs a{};
+    a.n_clouds = nclouds;
+    a.big_cap = (int32_t)big_cap;
+    a.xyz = d_xyz;
+    a.clouds = ensure<VoxelCloud>(v_clouds_, nclouds);
+    a.grids = ensure<VoxelGrid>(v_grids_, nclouds);
+    a.minmax = ensure<double>(v_minmax_, 6 * (size_t)chunks);
+    a.chunk_sums = ensure<int32_t>(v_sums_, 2 * (size_t)chunks);
+    a.table = ensure<VoxelSlot>(v_table_, (size_t)slots);
+    a.vid = ensure<int32_t>(v_vid_, (size_t)N);
+    a.members = ensure<int32_t>(v_members_, (size_t)N);
+    a.recs = ensure<VoxelRec>(v_recs_, (size_t)N);
+    a.big = ensure<int32_t>(v_big_, (size_t)big_cap);
+    int32_t* flags = ensure<int32_t>(v_flags_, nflags);
+    a.out_off = ensure<long long>(v_out_off_, (size_t)nclouds + 1);
+    if (!a.clouds || !a.grids || !a.minmax || !a.chunk_sums || !a.table || !a.vid ||
+        !a.members || !a.recs || !a.big || !flags || !a.out_off || h_vout_.reserve((size_t)nclouds + 1) ||
+        h_vflags_.reserve(nflags))
+        return SE3ICP_ERR_OUT_OF_MEMORY;
+    a.status = flags;
+    a.n_out = flags + nclouds;
+    a.error = flags + 2 * (size_t)nclouds;
+    a.n_big = a.error + 1;
+    a.out = d_out;
+    a.out_count = d_count;
+    a.out_first = d_first;
+    HIPCHK(hipMemcpyAsync(v_clouds_.p, (const VoxelCloud*)h_vclouds_, sizeof(VoxelCloud) * nclouds, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(flags, 0, sizeof(int32_t) * nflags, s));
+    launch_voxel(a, max_chunks, N, slots, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync((long long*)h_vout_, a.out_off, sizeof(long long) * ((size_t)nclouds + 1), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync((int32_t*)h_vflags_, flags, sizeof(int32_t) * nflags, hipMemcpyDeviceToHost, s));
+    SYNC_STREAM(s);
+    for (int c = 0; c < nclouds; ++c) {
+        const int32_t st = h_vflags_[c];
+        if (st == VOX_NONFINITE) return SE3ICP_ERR_NONFINITE;
+        if (st != VOX_OK) return SE3ICP_ERR_INVALID_ARG;  // too small a voxel, or a key past 63 bits
+    }
+    if (h_vflags_[2 * (size_t)nclouds] != 0) return SE3ICP_ERR_INTERNAL;
+    for (int c = 0; c <= nclouds; ++c) out_off[c] = (int64_t)h_vout_[c];
+    return 0;
+}
+
+int Engine::voxel_downsample_host(const double* xyz, int64_t n, double vs, double* out, int32_t* count, int32_t* first,
+                                  int64_t* n_out) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    if (!xyz || !n_out) return SE3ICP_ERR_INVALID_ARG;
+    if (n >= (int64_t)1 << 30) return SE3ICP_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(dev_));
+    double* d_in = ensure<double>(v_in_, 3 * (size_t)n);
+    double* d_o = ensure<double>(v_out_, 3 * (size_t)n);
+    int32_t* d_c = ensure<int32_t>(v_oc_, (size_t)n);
+    int32_t* d_f = ensure<int32_t>(v_of_, (size_t)n);
+    if (!d_in || !d_o || !d_c || !d_f) return SE3ICP_ERR_OUT_OF_MEMORY;
+    HIPCHK(hipMemcpyAsync(d_in, xyz, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, stream_));
+    const int64_t off[2] = {0, n};
+    int64_t oo[2] = {0, 0};
+    const int rc = voxel_downsample(1, d_in, off, &vs, d_o, oo, d_c, d_f, nullptr);
+    if (rc) return rc;
+    const size_t m = (size_t)oo[1];
+    if (out) HIPCHK(hipMemcpyAsync(out, d_o, sizeof(double) * 3 * m, hipMemcpyDeviceToHost, stream_));
+    if (count) HIPCHK(hipMemcpyAsync(count, d_c, sizeof(int32_t) * m, hipMemcpyDeviceToHost, stream_));
+    if (first) HIPCHK(hipMemcpyAsync(first, d_f, sizeof(int32_t) * m, hipMemcpyDeviceToHost, stream_));
+    if (out || count || first) SYNC_STREAM(stream_);
+    *n_out = oo[1];
+    return 0;
+}
+
 Engine* engine_for(int device) {
     static std::mutex reg_mu;
     static std::map<int, std::unique_ptr<Engine>> reg;

@@ -17,8 +17,12 @@
 #include "pairmath.hpp"
 #include "se3icp.h"
 #include "view.hpp"
+#include "voxel.hpp"
 
 namespace se3icp {
+
+// k_voxel.hip: queue the voxel-grid downsample of a call's clouds (voxel.hpp)
+void launch_voxel(const VoxelArgs& a, int max_chunks, int64_t n_points, int64_t n_slots, hipStream_t s);
 
 // A device buffer (Engine::ensure) and a pinned host mirror.  Each names the engine's list it
 // belongs to when it is declared: the destructor and the sweep's memory count walk those
@@ -128,6 +132,16 @@ class Engine {
     int estimate_normals(const double* xyz, int64_t n, int k, double* normals);
     int nn(const double* query, int64_t nq, const double* data, int64_t nd, int dim, int32_t* idx, double* d2,
            int32_t* num_rechecked);
+
+    // Voxel-grid downsample of nclouds clouds resident in HBM (cloud c: points off[c] .. off[c+1]
+    // of d_xyz, voxel size vs[c]) into d_out, compacted and contiguous; out_off [nclouds + 1] on
+    // the host.  d_count / d_first: optional device outputs per output voxel.  One wait, at the
+    // end.  The caller has validated the sizes (voxel_check_sizes).
+    int voxel_downsample(int nclouds, const double* d_xyz, const int64_t* off, const double* vs, double* d_out,
+                         int64_t* out_off, int32_t* d_count, int32_t* d_first, hipStream_t user_stream);
+    // The same for one host cloud: out / count / first are host arrays (any may be null); *n_out.
+    int voxel_downsample_host(const double* xyz, int64_t n, double vs, double* out, int32_t* count, int32_t* first,
+                              int64_t* n_out);
 
   private:
     struct CloudReq {
@@ -313,6 +327,14 @@ class Engine {
     std::vector<int32_t> tree_donor_;
     TreeTab tree_tab_a_{pins_, bufs_}, tree_tab_b_{pins_, bufs_}, tree_tab_12_{pins_, bufs_};
     int64_t tree_stats_[4] = {};
+    // voxel_downsample: the tables of VoxelArgs, the host's cloud table and what the call reads
+    // back (out_off, then the clouds' status, the error flag); voxel_downsample_host's staging
+    DevBuf v_clouds_{bufs_}, v_grids_{bufs_}, v_minmax_{bufs_}, v_sums_{bufs_}, v_table_{bufs_},
+        v_vid_{bufs_}, v_members_{bufs_}, v_recs_{bufs_}, v_big_{bufs_}, v_flags_{bufs_},
+        v_out_off_{bufs_}, v_in_{bufs_}, v_out_{bufs_}, v_oc_{bufs_}, v_of_{bufs_};
+    Pinned<VoxelCloud> h_vclouds_{pins_};
+    Pinned<long long> h_vout_{pins_};
+    Pinned<int32_t> h_vflags_{pins_};
     Pinned<PairDev> h_pairs_{pins_};
     Pinned<double> h_red_{pins_}, h_partial_{pins_};
     Pinned<int32_t> h_rechecked_{pins_};

@@ -18,7 +18,8 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            expand_edges, last_graph_stats, register_graph, register_graph_device,
                            register_graph_report, register_graph_traced, register_sequence, sequence_edges,
                            set_batch_sharing, set_lrf_seeding, last_seed_stats,
-                           set_tree_sharing, last_tree_stats)
+                           set_tree_sharing, last_tree_stats,
+                           voxel_downsample, voxel_downsample_device)
 from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
@@ -31,4 +32,5 @@ __all__ = [
     "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
     "register_graph_report", "register_graph_traced", "last_graph_stats",
     "set_batch_sharing", "set_lrf_seeding", "last_seed_stats", "set_tree_sharing", "last_tree_stats",
+    "voxel_downsample", "voxel_downsample_device",
 ]

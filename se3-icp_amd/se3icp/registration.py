@@ -659,11 +659,15 @@ def _edge_arrays(edges):
 
 
 def register_graph(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
-                   sharing: int = 0) -> list[PairResult]:
+                   sharing: int = 0, voxel_size: float | None = None) -> list[PairResult]:
     """Register clouds[s] onto clouds[t] for every (s, t) of `edges`: result p is bitwise
     register_batch's for that pair, but every distinct cloud is uploaded and ingested once and
     set up once per normalization it takes part in (se3icp_register_graph).  sharing: 0 the
-    engine's choice, 1 .. 3 see include/se3icp.h."""
+    engine's choice, 1 .. 3 see include/se3icp.h.  voxel_size: the clouds are raw scans; each is
+    uploaded once, voxel-downsampled in HBM (voxel_downsample_device) and the result registered
+    by the device entry -- bitwise register_graph of the clouds voxel_downsample returns."""
+    if voxel_size is not None:
+        return _register_graph_voxel(clouds, edges, method, params, device, sharing, float(voxel_size))
     _keep, cargs = _cloud_args(clouds)
     n, es, et = _edge_arrays(edges)
     res, _ = _outputs(n)
@@ -673,9 +677,9 @@ def register_graph(clouds, edges, method: str, params: _lib.Params | None = None
 
 
 def register_sequence(clouds, method: str, params: _lib.Params | None = None, device: int = 0,
-                      sharing: int = 0) -> list[PairResult]:
+                      sharing: int = 0, voxel_size: float | None = None) -> list[PairResult]:
     """register_graph over sequence_edges(len(clouds)): scan i+1 onto scan i."""
-    return register_graph(clouds, sequence_edges(len(clouds)), method, params, device, sharing)
+    return register_graph(clouds, sequence_edges(len(clouds)), method, params, device, sharing, voxel_size)
 
 
 def register_graph_device(xyz_ptr: int, off, edges, method: str, params: _lib.Params | None = None,
@@ -712,6 +716,66 @@ def register_graph_traced(clouds, edges, method: str, params: _lib.Params | None
     with _armed_trace(device, edge, _as_xyz(clouds[int(edges[edge][0])]).shape[0], max_iters) as trace:
         res = register_graph(clouds, edges, method, params, device, sharing)
     return res, trace
+
+
+# ---- voxel-grid downsample (raw scans -> the clouds the drivers register)
+_IP = C.POINTER(C.c_int32)
+
+
+def voxel_downsample(xyz, voxel_size: float, device: int = 0, return_counts: bool = False):
+    """Open3D ``PointCloud::VoxelDownSample`` of one (N, 3) cloud on the GPU
+    (se3icp_voxel_downsample): the (M, 3) voxel means, voxels in first-occurrence order.
+    return_counts: also the points per voxel and each voxel's lowest input index, (M,) int32."""
+    pts = _as_xyz(xyz)
+    n = pts.shape[0]
+    out = np.empty((max(n, 1), 3))
+    cnt = np.empty(max(n, 1), dtype=np.int32)
+    fst = np.empty(max(n, 1), dtype=np.int32)
+    m = _lib.load().se3icp_voxel_downsample(int(device), pts.ctypes.data_as(_DP), n, float(voxel_size),
+                                            out.ctypes.data_as(_DP), cnt.ctypes.data_as(_IP) if return_counts else None,
+                                            fst.ctypes.data_as(_IP) if return_counts else None)
+    if m < 0:
+        raise _lib.Se3IcpError(int(m), "voxel_downsample")
+    if return_counts:
+        return out[:m].copy(), cnt[:m].copy(), fst[:m].copy()
+    return out[:m].copy()
+
+
+def voxel_downsample_device(xyz_ptr: int, off, voxel_size, out_ptr: int, device: int = 0, stream: int = 0,
+                            count_ptr: int = 0, first_ptr: int = 0) -> list[int]:
+    """Voxel-downsample clouds resident in HBM into HBM (se3icp_voxel_downsample_device).
+
+    xyz_ptr: device address of the concatenated AoS float64 xyz; off: n_clouds+1 point offsets;
+    voxel_size: one value, or one per cloud; out_ptr: device buffer with room for every input
+    point.  Returns out_off (n_clouds+1): (out_ptr, out_off) go straight into
+    register_batch_device / register_graph_device.  count_ptr / first_ptr: optional int32
+    device buffers (points per output voxel, its lowest input index within its cloud)."""
+    nc = len(off) - 1
+    vs = np.ascontiguousarray(np.broadcast_to(np.asarray(voxel_size, dtype=np.float64), (max(nc, 0),)))
+    co = (C.c_int64 * (max(nc, 0) + 1))(*[int(x) for x in off])
+    oo = (C.c_int64 * (max(nc, 0) + 1))()
+    _lib.check(_lib.load().se3icp_voxel_downsample_device(
+        int(device), nc, C.c_void_p(xyz_ptr), co, vs.ctypes.data_as(_DP), C.c_void_p(out_ptr), oo,
+        C.c_void_p(count_ptr) if count_ptr else None, C.c_void_p(first_ptr) if first_ptr else None,
+        _stream_arg(stream)), "voxel_downsample_device")
+    return [int(x) for x in oo]
+
+
+def _register_graph_voxel(clouds, edges, method, params, device, sharing, voxel_size):
+    """register_graph(voxel_size=...): the raw clouds go to HBM once (torch holds the buffers),
+    are downsampled there and registered where they lie."""
+    import torch
+
+    cl = [_as_xyz(c) for c in clouds]
+    off = np.concatenate([[0], np.cumsum([a.shape[0] for a in cl])]).astype(np.int64)
+    if len(cl) == 0 or off[-1] == 0:
+        raise _lib.Se3IcpError(_lib.ERR_EMPTY_CLOUD, "register_graph(voxel_size=...)")
+    dev = torch.device("cuda", int(device) & 0xff)
+    raw = torch.from_numpy(np.concatenate(cl)).to(dev)
+    down = torch.empty_like(raw)
+    torch.cuda.synchronize(dev)  # the engine's stream is not torch's
+    out_off = voxel_downsample_device(raw.data_ptr(), off, voxel_size, down.data_ptr(), device=device)
+    return register_graph_device(down.data_ptr(), out_off, edges, method, params, device=device, sharing=sharing)
 
 
 def last_graph_stats(device: int = 0) -> dict:

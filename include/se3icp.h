@@ -394,6 +394,78 @@ int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const doubl
 int se3icp_request_report(se3icp_registration* r, const se3icp_report_options* opts);
 int se3icp_get_report(const se3icp_registration* r, se3icp_report* out);
 
+/* ------------------------------------------------------------- initial poses
+ * What Open3D's RegistrationICP(source, target, d, init) and PCL's align(out, guess) take: a
+ * pose to start from -- the odometry prior of a chain, the chained odometry of a loop-closure
+ * edge, the last pose of a scan against a map.  A pose is a row-major 4x4 f64 matrix, source
+ * frame -> target frame, bottom row (0, 0, 0, 1).  The arithmetic is Open3D's Transform and is
+ * pinned (csrc/pose.hpp), every step one IEEE f64 operation, no FMA, no division:
+ *   apply_pose(M, p)  q[e]    = ((M[4e]*p0 + M[4e+1]*p1) + M[4e+2]*p2) + M[4e+3]*1.0     e = 0..2
+ *   compose(A, B)     C[i][j] = ((A[i][0]*B[0][j] + A[i][1]*B[1][j]) + A[i][2]*B[2][j]) + A[i][3]*B[3][j]
+ *                     for rows 0..2, row 3 exactly (0, 0, 0, 1)
+ *
+ * se3icp_register_graph_init(_device): se3icp_register_graph(_report)(_device) with one pose per
+ * edge.  With T_init[p] = T0, results[p] is BITWISE what the plain entry returns for the pair
+ * (X', target), X' = apply_pose(T0, X) for every point of the source, except T, which is
+ * compose(T_plain, T0); both iteration counts, status and scaling_factor are the plain run's on
+ * X', and so is a report, per-point outputs included.  X' is never written out: the engine folds
+ * the pose into the one read it makes of the raw cloud, and with host buffers every raw cloud is
+ * uploaded once however many poses it is used under (se3icp_last_graph_stats: `clouds` and
+ * `bytes uploaded` count the distinct RAW clouds).
+ * A T0 that is bitwise the identity (zeros +0.0) means "no pose": that edge's source is the raw
+ * cloud itself (X, not apply_pose(I, X), which would turn -0.0 into +0.0) and shares its classes,
+ * seeds and tree orders with the cloud's other uses.  T_init == NULL is the plain entry, launch
+ * for launch.  Equal pose bits on one cloud are one posed copy; kd-tree orders are adopted
+ * between the slots of one (cloud, pose) only.
+ * se3_gicp_with_cf, A STATED DEPARTURE: the lounge confidences are depths in the camera frame, a
+ * sensor quantity, and come from the RAW z of the source.  The equality with the plain entry on
+ * X' holds for a T0 that leaves z bitwise unchanged (third row exactly (0, 0, 1, 0)); for any
+ * other T0 the call is the plain run on X' with the source's confidences taken from X.
+ * opts and reports: both NULL (no report) or both given; exactly one NULL is
+ * SE3ICP_ERR_INVALID_ARG.  Checked with the other arguments, before the device is looked up:
+ * SE3ICP_ERR_INVALID_ARG for a non-finite entry of a pose or a bottom row that is not bitwise
+ * (0, 0, 0, 1).  The 3x3 block is not checked: a block that is not orthonormal is applied as given,
+ * as Open3D does, and only keeps that copy out of the seeding below.
+ * se3icp_set_trace before a posed call records the plain run on X'. */
+int se3icp_init_version(void);  /* 1 */
+int se3icp_register_graph_init(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                               int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud,
+                               const double* T_init /* n_pairs * 16, or NULL */, int method,
+                               const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                               const se3icp_report_options* opts, se3icp_report* reports);
+int se3icp_register_graph_init_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                      int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud,
+                                      const double* T_init /* host, n_pairs * 16, or NULL */, int method,
+                                      const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                                      void* hip_stream, const se3icp_report_options* opts, se3icp_report* reports);
+/* Object surface: every later run_* of the object starts from T and returns the posed result
+ * (current_estimated_T_ is the composed pose; a requested report follows).  T == NULL clears. */
+int se3icp_set_initial_transform(se3icp_registration* r, const double* T);
+/* A posed copy of a cloud is the cloud moved rigidly, so under the run_se3_* normalization its
+ * neighbour distances are the raw cloud's up to rounding: the first selecting class of a raw
+ * cloud, under whatever pose, seeds the later classes of all its copies whose pose is rigid
+ * (max |R^T R - I| <= 2^-30), exactly as se3icp_set_lrf_seeding describes for the classes of one
+ * cloud -- self-certifying, bitwise the unseeded results; its modes 1-3 act on these seeds too.
+ * mode: 0 seeded across poses (the default of every engine), 1 within one (cloud, pose) only.
+ * Anything else is SE3ICP_ERR_INVALID_ARG, checked before the device is looked up. */
+int se3icp_set_pose_seeding(int device, int mode);
+/* Of the last graph call on `device`: out[SE3ICP_INIT_STATS_N], n >= that (else
+ * SE3ICP_ERR_INVALID_ARG) = {edges with a pose, posed copies ingested, classes seeded from a class
+ * of another pose of their cloud}. */
+#define SE3ICP_INIT_STATS_N 3
+int se3icp_last_init_stats(int device, int64_t* out, int n);
+/* out[i] = apply_pose(T, xyz[i]) for n points on the host (no device needed); out may be xyz.
+ * SE3ICP_ERR_INVALID_ARG for a pose that is not valid (above), a NULL array with n > 0, n < 0. */
+int se3icp_transform_points(const double* T, const double* xyz, int64_t n, double* out);
+/* One pose per cloud applied to clouds resident in HBM, every cloud in one launch (T: host,
+ * n_clouds * 16; d_xyz / off as se3icp_register_graph_device; d_out laid out as d_xyz): what puts
+ * registered scans into one frame.  d_out == d_xyz is allowed; any other overlap of the two
+ * ranges is SE3ICP_ERR_INVALID_ARG, as are an invalid pose, a NULL array, n_clouds <= 0 or over
+ * 65,535 and a decreasing off -- all before the device is looked up.  Kernels run on hip_stream
+ * (NULL = the engine's own stream); the call waits once, at its end. */
+int se3icp_transform_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off, const double* T,
+                            double* d_out, void* hip_stream);
+
 /* Single pair convenience (host buffers). */
 int se3icp_register(int device, const double* src_xyz, int64_t n_src, const double* tgt_xyz, int64_t n_tgt,
                     int method, const se3icp_params* params, se3icp_result* result);

@@ -11,6 +11,7 @@
 
 #include "engine.hpp"
 #include "graph.hpp"
+#include "pose.hpp"
 #include "se3icp.h"
 
 using se3icp::Engine;
@@ -58,6 +59,9 @@ struct se3icp_registration {
     bool want_report = false, have_report = false;
     se3icp_report_options ropts{};
     se3icp_report rep{};
+    // se3icp_set_initial_transform: the pose every run_* starts from
+    bool have_init = false;
+    double init[16] = {};
 };
 
 extern "C" {
@@ -283,7 +287,8 @@ int se3icp_register_sweep_report_device(int device, int32_t n_pairs, const doubl
 static int graph_run(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts, bool on_device,
                      int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, int method,
                      const se3icp_params* params, int32_t sharing, se3icp_result* results, void* hip_stream,
-                     bool with_report, const se3icp_report_options* opts, se3icp_report* reports) {
+                     bool with_report, const se3icp_report_options* opts, se3icp_report* reports,
+                     const double* T_init = nullptr) {
     if (with_report) {
         const int rc = report_check(opts, reports, true);
         if (rc) return rc;
@@ -294,12 +299,16 @@ static int graph_run(int device, int32_t n_clouds, const double* const* xyz, con
     if (method >= SE3ICP_SE3_PT2PT && params && params->number_of_nn_for_LRF <= 0) return SE3ICP_ERR_INVALID_ARG;
     for (int32_t p = 0; p < n_pairs; ++p)
         if (!xyz[src_cloud[p]] || !xyz[tgt_cloud[p]]) return SE3ICP_ERR_INVALID_ARG;
+    if (T_init)
+        for (int32_t p = 0; p < n_pairs; ++p)
+            if (!se3icp::pose_is_valid(T_init + 16 * (size_t)p)) return SE3ICP_ERR_INVALID_ARG;
     Engine* e = usable_engine(device);
     if (!e) return SE3ICP_ERR_NO_DEVICE;
     const se3icp_params p = params_or_defaults(params);
     std::lock_guard<std::mutex> lk(e->mutex());
     return e->register_graph(n_clouds, xyz, n_pts, n_pairs, src_cloud, tgt_cloud, on_device, method, p, sharing, results,
-                             (hipStream_t)hip_stream, with_report ? opts : nullptr, with_report ? reports : nullptr);
+                             (hipStream_t)hip_stream, with_report ? opts : nullptr, with_report ? reports : nullptr,
+                             T_init);
 }
 
 // the per-cloud pointers and sizes of clouds concatenated in HBM
@@ -354,6 +363,75 @@ int se3icp_register_graph_report_device(int device, int32_t n_clouds, const doub
     if (rc) return rc;
     return graph_run(device, n_clouds, x.data(), n.data(), true, n_pairs, src_cloud, tgt_cloud, method, params, sharing,
                      results, hip_stream, true, opts, reports);
+}
+
+// ------------------------------------------------------------------ initial poses
+int se3icp_init_version(void) { return 1; }
+
+int se3icp_register_graph_init(int device, int32_t n_clouds, const double* const* xyz, const int64_t* n_pts,
+                               int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud, const double* T_init,
+                               int method, const se3icp_params* params, int32_t sharing, se3icp_result* results,
+                               const se3icp_report_options* opts, se3icp_report* reports) {
+    if (!xyz || (opts == nullptr) != (reports == nullptr)) return SE3ICP_ERR_INVALID_ARG;
+    return graph_run(device, n_clouds, xyz, n_pts, false, n_pairs, src_cloud, tgt_cloud, method, params, sharing, results,
+                     nullptr, opts != nullptr, opts, reports, T_init);
+}
+
+int se3icp_register_graph_init_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off,
+                                      int32_t n_pairs, const int32_t* src_cloud, const int32_t* tgt_cloud,
+                                      const double* T_init, int method, const se3icp_params* params, int32_t sharing,
+                                      se3icp_result* results, void* hip_stream, const se3icp_report_options* opts,
+                                      se3icp_report* reports) {
+    if ((opts == nullptr) != (reports == nullptr)) return SE3ICP_ERR_INVALID_ARG;
+    std::vector<const double*> x;
+    std::vector<int64_t> n;
+    const int rc = cloud_ranges(n_clouds, d_xyz, off, x, n);
+    if (rc) return rc;
+    return graph_run(device, n_clouds, x.data(), n.data(), true, n_pairs, src_cloud, tgt_cloud, method, params, sharing,
+                     results, hip_stream, opts != nullptr, opts, reports, T_init);
+}
+
+int se3icp_set_pose_seeding(int device, int mode) {
+    if (mode < se3icp::kPoseSeedingMin || mode > se3icp::kPoseSeedingMax) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_pose_seeding(mode);
+    return SE3ICP_OK;
+}
+
+int se3icp_last_init_stats(int device, int64_t* out, int n) {
+    if (!out || n < se3icp::IS_COUNT) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    for (int k = 0; k < se3icp::IS_COUNT; ++k) out[k] = e->init_stats()[k];
+    return SE3ICP_OK;
+}
+
+int se3icp_transform_points(const double* T, const double* xyz, int64_t n, double* out) {
+    if (!T || n < 0 || (n > 0 && (!xyz || !out)) || !se3icp::pose_is_valid(T)) return SE3ICP_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; ++i) se3icp::apply_pose(T, xyz + 3 * i, out + 3 * i);
+    return SE3ICP_OK;
+}
+
+int se3icp_transform_device(int device, int32_t n_clouds, const double* d_xyz, const int64_t* off, const double* T,
+                            double* d_out, void* hip_stream) {
+    if (n_clouds <= 0 || n_clouds > 65535 || !d_xyz || !off || !T || !d_out) return SE3ICP_ERR_INVALID_ARG;
+    for (int32_t c = 0; c < n_clouds; ++c)
+        if (off[c + 1] < off[c] || !se3icp::pose_is_valid(T + 16 * (size_t)c)) return SE3ICP_ERR_INVALID_ARG;
+    // in place, or apart: a partial overlap would have one block read what another has written
+    if (d_out != d_xyz) {
+        const double* lo = d_xyz + 3 * off[0];
+        const double* hi = d_xyz + 3 * off[n_clouds];
+        const double* olo = d_out + 3 * off[0];
+        const double* ohi = d_out + 3 * off[n_clouds];
+        if (olo < hi && lo < ohi) return SE3ICP_ERR_INVALID_ARG;
+    }
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    return e->transform_device(n_clouds, d_xyz, off, T, d_out, (hipStream_t)hip_stream);
 }
 
 int se3icp_last_graph_stats(int device, int64_t* out, int n) {
@@ -449,6 +527,21 @@ static int run_object(se3icp_registration* r, int method) {
     const double* t = r->tgt.data();
     se3icp_result res;
     se3icp_report rep;
+    if (r->have_init) {
+        // (a graph of the two clouds and the one edge: bitwise the batch, se3icp_register_graph)
+        const double* const xyz[2] = {s, t};
+        const int64_t n[2] = {ns, nt};
+        const int32_t es = 0, et = 1;
+        const int rc = se3icp_register_graph_init(current_device(), 2, xyz, n, 1, &es, &et, r->init, method, &r->prm, 0,
+                                                  &res, r->want_report ? &r->ropts : nullptr,
+                                                  r->want_report ? &rep : nullptr);
+        if (rc == SE3ICP_OK || rc == SE3ICP_ERR_NONFINITE) {
+            r->res = res;
+            r->have_report = r->want_report;
+            if (r->want_report) r->rep = rep;
+        }
+        return rc;
+    }
     int rc = r->want_report ? se3icp_register_batch_report(current_device(), 1, &s, &ns, &t, &nt, method, &r->prm, &res,
                                                            &r->ropts, &rep)
                             : se3icp_register_batch(current_device(), 1, &s, &ns, &t, &nt, method, &r->prm, &res);
@@ -514,6 +607,18 @@ int se3icp_run_se3_pure(se3icp_registration* r, const char* variant) {
     const int rc = run_object(r, SE3ICP_SE3_PURE_PT2PT + v);
     if (rc == SE3ICP_OK || rc == SE3ICP_ERR_NONFINITE) std::cout << "pure se3 finished" << std::endl;  // ISR.cpp:1127
     return rc;
+}
+
+int se3icp_set_initial_transform(se3icp_registration* r, const double* T) {
+    if (!r) return SE3ICP_ERR_INVALID_ARG;
+    if (!T) {
+        r->have_init = false;
+        return 0;
+    }
+    if (!se3icp::pose_is_valid(T)) return SE3ICP_ERR_INVALID_ARG;
+    std::memcpy(r->init, T, sizeof(r->init));
+    r->have_init = true;
+    return 0;
 }
 
 int se3icp_get_result(const se3icp_registration* r, se3icp_result* out) {

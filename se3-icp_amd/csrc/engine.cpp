@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "graph.hpp"
+#include "pose.hpp"
 #include "report.hpp"
 #include "sweep.hpp"
 #include "tree.hpp"
@@ -632,6 +633,8 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
     se3icp_trace* tr = c->tr = trace_;  // one-shot: the record covers this call only
     trace_ = nullptr;
+    pose_raw_.clear();  // (a call without a posed edge plans its seeds over clouds)
+    pose_rigid_.clear();
     if (args) return args;
     if (tr && (tr->pair < 0 || (int64_t)tr->pair >= nslots || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
     if (tr) tr->iters_recorded = 0;
@@ -883,7 +886,11 @@ int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>
             nn[k] = h_clouds_[home[k]].n;
         }
         std::vector<SeedClass> sc;
-        const int seeded = graph_plan_seeds(plan, kk.data(), nn.data(), &sc);
+        int32_t cross = 0;
+        const int seeded = pose_raw_.empty()
+                               ? graph_plan_seeds(plan, kk.data(), nn.data(), &sc)
+                               : graph_plan_seeds_posed(plan, kk.data(), nn.data(), pose_raw_.data(), pose_rigid_.data(),
+                                                        pose_seeding_ == 0, &sc, &cross);
         int64_t total = 0;
         for (int k = 0; k < K; ++k)
             if (sc[k].from >= 0) total += nn[k];  // (an upper bound of the buffer: a source may seed several)
@@ -900,6 +907,7 @@ int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>
                 seed_ref_[home[k]].rho2 = sc[k].rho2;
             }
             seed_stats_[0] = seeded;
+            init_stats_[IS_CROSS_SEEDED] = cross;
             seed_on_ = true;
         }
     }
@@ -1510,16 +1518,46 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
 int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts, int P, const int32_t* esrc,
                            const int32_t* etgt, bool on_device, int method, const se3icp_params& prm, int sharing,
                            se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts,
-                           se3icp_report* reports) {
+                           se3icp_report* reports, const double* T_init) {
     // ---- layouts A (used clouds, in cloud order) and B (uses)
     const int args = (C <= 0 || P <= 0 || !xyz || !npts || !esrc || !etgt || !out) ? SE3ICP_ERR_INVALID_ARG : 0;
     MethodPlan mp{};
     std::vector<int32_t> slotA, cloudA;
     int rest = args ? 0 : plan_method(method, prm.number_of_nn_for_LRF, &mp);
+    // Initial poses: the call is planned over VARIANTS (graph.hpp) instead of clouds.  C, xyz, npts,
+    // esrc and etgt are rebound to the variants' -- numbered by first use -- and layout A becomes
+    // "every used variant once"; everything below reads them as it reads clouds.  Without a posed
+    // edge (T_init null, or every pose bitwise the identity) nothing is rebound: the plain call.
+    VariantPlan vplan;
+    std::vector<const double*> vxyz;
+    std::vector<int64_t> vnpts;
+    const int rawC = C;
+    const double* const* rawxyz = xyz;
+    const int64_t* rawnpts = npts;
+    if (!args && !rest && T_init) {
+        std::vector<int32_t> slotR, cloudR;  // (the clouds' own checks, before anything is rebound)
+        rest = graph_used_clouds(C, xyz, npts, P, esrc, etgt, &slotR, &cloudR);
+        if (!rest) graph_plan_variants(P, esrc, etgt, T_init, &vplan);
+    }
+    const bool posed = vplan.posed_edges > 0;
+    if (posed) {
+        C = (int)vplan.cloud.size();
+        vxyz.resize(C);
+        vnpts.resize(C);
+        for (int v = 0; v < C; ++v) {
+            vxyz[v] = rawxyz[vplan.cloud[v]];
+            vnpts[v] = rawnpts[vplan.cloud[v]];
+        }
+        xyz = vxyz.data();
+        npts = vnpts.data();
+        esrc = vplan.edge_src.data();
+        etgt = vplan.edge_tgt.data();
+    }
     if (!args && !rest) rest = graph_used_clouds(C, xyz, npts, P, esrc, etgt, &slotA, &cloudA);
     Call call;
     int rc = open_call(args, P, rest, user_stream, &call);
     if (rc) return rc;
+    for (int64_t& g : init_stats_) g = 0;
     hipStream_t s = call.s;
     const bool se3 = mp.se3;
     if (sharing == 0) sharing = 3;
@@ -1558,12 +1596,62 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
         reqA[a].st.alpha = reqA[a].st.beta = reqA[a].st.norm_scale = 1.0;
         if (!on_device) graph_stats_[GS_BYTES_UPLOADED] += (int64_t)sizeof(double) * 3 * reqA[a].n;
     }
-    rc = upload_clouds(reqA, on_device, s);
+    int rawCA = CA;  // the distinct raw clouds among A's slots
+    if (posed) {
+        // every raw cloud is uploaded once, however many variants it has: the variants' inputs point
+        // at their cloud's one copy (d_in_ has room for NU >= the raw clouds' points)
+        std::vector<const double*> d_raw(rawC, nullptr);
+        int64_t up = 0;
+        rawCA = 0;
+        graph_stats_[GS_BYTES_UPLOADED] = 0;
+        for (int a = 0; a < CA; ++a) {
+            const int c = vplan.cloud[cloudA[a]];
+            if (!d_raw[c]) {
+                ++rawCA;
+                if (on_device) {
+                    d_raw[c] = rawxyz[c];
+                } else {
+                    double* dst = (double*)d_in_.p + 3 * (size_t)up;
+                    HIPCHK(hipMemcpyAsync(dst, rawxyz[c], sizeof(double) * 3 * rawnpts[c], hipMemcpyHostToDevice, s));
+                    d_raw[c] = dst;
+                    up += rawnpts[c];
+                    graph_stats_[GS_BYTES_UPLOADED] += (int64_t)sizeof(double) * 3 * rawnpts[c];
+                }
+            }
+            reqA[a].in = d_raw[c];
+        }
+    }
+    rc = upload_clouds(reqA, on_device || posed, s);
     if (rc) return rc;
     const std::vector<CloudDev> clA = h_clouds_;
     const int nchA = (int)h_chunks_.size();
     View v = view();
-    launch_ingest(v, (const ChunkWork*)d_chunks_.p, nchA, (double*)d_partial_.p, s);
+    if (posed) {
+        // the posed ingest: A's slot a is its raw cloud read through the pose of its variant
+        pose_of_.assign(CA, -1);
+        pose_tab_.clear();
+        pose_raw_.assign(C, 0);
+        pose_rigid_.assign(C, 1);
+        for (int a = 0; a < CA; ++a) {
+            const int vv = cloudA[a];
+            pose_raw_[vv] = vplan.cloud[vv];
+            if (vplan.pose_edge[vv] < 0) continue;
+            const double* M = T_init + 16 * (size_t)vplan.pose_edge[vv];
+            pose_of_[a] = (int32_t)(pose_tab_.size() / 16);
+            pose_tab_.insert(pose_tab_.end(), M, M + 16);
+            pose_rigid_[vv] = pose_is_rigid(M) ? 1 : 0;
+        }
+        if (!ensure<int32_t>(d_pose_of_, CA) || !ensure<double>(d_pose_tab_, pose_tab_.size()))
+            return SE3ICP_ERR_OUT_OF_MEMORY;
+        HIPCHK(hipMemcpyAsync(d_pose_of_.p, pose_of_.data(), sizeof(int32_t) * CA, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_pose_tab_.p, pose_tab_.data(), sizeof(double) * pose_tab_.size(), hipMemcpyHostToDevice, s));
+        launch_ingest_posed(v, (const ChunkWork*)d_chunks_.p, nchA, (double*)d_partial_.p, (const int32_t*)d_pose_of_.p,
+                            (const double*)d_pose_tab_.p, s);
+        init_stats_[IS_EDGES] = vplan.posed_edges;
+        init_stats_[IS_VARIANTS] = vplan.posed_variants;
+    } else {
+        launch_ingest(v, (const ChunkWork*)d_chunks_.p, nchA, (double*)d_partial_.p, s);
+    }
     HIPCHK(hipGetLastError());
     std::vector<double> cenC(3 * (size_t)C, 0.0), radC(C, 0.0);  // by the call's cloud index
     if (se3) {
@@ -1597,7 +1685,7 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
     graph_plan(P, esrc, etgt, se3, prm.scale_preprocessing, cenC.data(), radC.data(), mp.k_nrm_s, mp.k_nrm_t,
                sharing >= 2, &plan);
     const int K = (int)plan.classes.size();
-    graph_stats_[GS_CLOUDS] = CA;
+    graph_stats_[GS_CLOUDS] = rawCA;
     graph_stats_[GS_USES] = 2 * (int64_t)P;
     graph_stats_[GS_CLASSES] = K;
 
@@ -1671,7 +1759,18 @@ int Engine::register_graph(int C, const double* const* xyz, const int64_t* npts,
     if (rc) return rc;
     rc = select_by_class(plan, stU, mp, s);
     if (rc) return rc;
-    return run_pairs(mp, P, ns.data(), nt.data(), &prm, P, false, call, out, ropts, reports);
+    rc = run_pairs(mp, P, ns.data(), nt.data(), &prm, P, false, call, out, ropts, reports);
+    if (posed && (rc == 0 || rc == SE3ICP_ERR_NONFINITE)) {
+        // the pose of the raw source: the de-normalized result on the posed source, then the pose
+        for (int p = 0; p < P; ++p) {
+            const int vv = vplan.edge_src[p];
+            if (vplan.pose_edge[vv] < 0) continue;
+            double Tc[16];
+            compose(out[p].T, T_init + 16 * (size_t)vplan.pose_edge[vv], Tc);
+            std::memcpy(out[p].T, Tc, sizeof(Tc));
+        }
+    }
+    return rc;
 }
 
 // Row it-1 of the armed trace after iteration `it` completed (the stream is idle: the
@@ -2001,6 +2100,35 @@ int Engine::voxel_downsample_host(const double* xyz, int64_t n, double vs, doubl
     if (first) HIPCHK(hipMemcpyAsync(first, d_f, sizeof(int32_t) * m, hipMemcpyDeviceToHost, stream_));
     if (out || count || first) SYNC_STREAM(stream_);
     *n_out = oo[1];
+    return 0;
+}
+
+// ----------------------------------------------------------------------------- transform stage
+int Engine::transform_device(int nclouds, const double* d_xyz, const int64_t* off, const double* T, double* d_out,
+                             hipStream_t user_stream) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    if (!d_xyz || !d_out || !off || !T || nclouds <= 0) return SE3ICP_ERR_INVALID_ARG;
+    if (nclouds > 65535) return SE3ICP_ERR_INVALID_ARG;  // one grid row per cloud
+    HIPCHK(hipSetDevice(dev_));
+    hipStream_t s = user_stream ? user_stream : stream_;
+    if (h_tf_clouds_.reserve(nclouds) || h_tf_poses_.reserve(16 * (size_t)nclouds)) return SE3ICP_ERR_OUT_OF_MEMORY;
+    PoseCloud* dc = ensure<PoseCloud>(d_tf_clouds_, nclouds);
+    double* dp = ensure<double>(d_tf_poses_, 16 * (size_t)nclouds);
+    if (!dc || !dp) return SE3ICP_ERR_OUT_OF_MEMORY;
+    int64_t max_n = 0;
+    for (int c = 0; c < nclouds; ++c) {
+        const int64_t n = off[c + 1] - off[c];
+        h_tf_clouds_[c] = PoseCloud{(long long)off[c], (long long)n};
+        max_n = std::max(max_n, n);
+    }
+    std::memcpy((double*)h_tf_poses_, T, sizeof(double) * 16 * (size_t)nclouds);
+    const int64_t max_chunks = (max_n + kPoseChunk - 1) / kPoseChunk;
+    if (max_chunks > INT32_MAX) return SE3ICP_ERR_INVALID_ARG;
+    HIPCHK(hipMemcpyAsync(dc, (const PoseCloud*)h_tf_clouds_, sizeof(PoseCloud) * nclouds, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dp, (const double*)h_tf_poses_, sizeof(double) * 16 * (size_t)nclouds, hipMemcpyHostToDevice, s));
+    launch_transform(d_xyz, d_out, dc, dp, nclouds, (int)max_chunks, s);
+    HIPCHK(hipGetLastError());
+    SYNC_STREAM(s);  // (the pinned tables are the next call's too)
     return 0;
 }
 

@@ -15,6 +15,7 @@
 
 #include "graph.hpp"
 #include "pairmath.hpp"
+#include "pose.hpp"
 #include "se3icp.h"
 #include "view.hpp"
 #include "voxel.hpp"
@@ -111,10 +112,22 @@ class Engine {
     // ingested once and every (cloud, normalization) class selects its neighbours once
     // (graph.hpp); results[p] is bitwise register_batch's for that pair.  The caller has
     // validated the arguments.
+    // T_init (validated by the caller; may be null): one row-major 4x4 initial pose per edge, source
+    // frame -> target frame.  results[p] is then bitwise the plain call's for (apply_pose(T0, source),
+    // target) except T, which is compose(T_plain, T0).  The call is planned over variants
+    // (graph.hpp): a posed variant is ingested from its raw cloud through the pose and is a cloud
+    // of its own to everything behind the ingest.
     int register_graph(int nclouds, const double* const* xyz, const int64_t* npts, int npairs, const int32_t* src,
                        const int32_t* tgt, bool on_device, int method, const se3icp_params& prm, int sharing,
                        se3icp_result* out, hipStream_t user_stream, const se3icp_report_options* ropts = nullptr,
-                       se3icp_report* reports = nullptr);
+                       se3icp_report* reports = nullptr, const double* T_init = nullptr);
+    // [IS_COUNT] of the last register_graph (se3icp_last_init_stats)
+    const int64_t* init_stats() const { return init_stats_; }
+    void set_pose_seeding(int mode) { pose_seeding_ = mode; }
+    // One pose per cloud applied to clouds resident in HBM, all in one launch (k_pose.hip); T on
+    // the host; d_out may be d_xyz.  The caller has validated the arguments.  One wait, at the end.
+    int transform_device(int nclouds, const double* d_xyz, const int64_t* off, const double* T, double* d_out,
+                         hipStream_t user_stream);
     // [GS_COUNT] of the last register_graph, or of the last device batch that looked for shared
     // clouds (setup_pairs_shared)
     const int64_t* graph_stats() const { return graph_stats_; }
@@ -327,6 +340,19 @@ class Engine {
     std::vector<int32_t> tree_donor_;
     TreeTab tree_tab_a_{pins_, bufs_}, tree_tab_b_{pins_, bufs_}, tree_tab_12_{pins_, bufs_};
     int64_t tree_stats_[4] = {};
+    // register_graph with initial poses: the pose of every slot of layout A (-1: none) and the
+    // poses' table, on the host until the call's last synchronisation and on the device; per
+    // variant its raw cloud and whether its pose is rigid (select_by_class: graph_plan_seeds_posed;
+    // empty in a call without a posed edge); se3icp_set_pose_seeding (0 across variants, 1 off)
+    std::vector<int32_t> pose_of_, pose_raw_, pose_rigid_;
+    std::vector<double> pose_tab_;
+    DevBuf d_pose_of_{bufs_}, d_pose_tab_{bufs_};
+    int pose_seeding_ = 0;
+    int64_t init_stats_[3] = {};
+    // transform_device: the clouds' ranges and poses (pinned: async copies), their device copies
+    Pinned<PoseCloud> h_tf_clouds_{pins_};
+    Pinned<double> h_tf_poses_{pins_};
+    DevBuf d_tf_clouds_{bufs_}, d_tf_poses_{bufs_};
     // voxel_downsample: the tables of VoxelArgs, the host's cloud table and what the call reads
     // back (out_off, then the clouds' status, the error flag); voxel_downsample_host's staging
     DevBuf v_clouds_{bufs_}, v_grids_{bufs_}, v_minmax_{bufs_}, v_sums_{bufs_}, v_table_{bufs_},

@@ -185,6 +185,113 @@ inline int32_t graph_plan_seeds(const GraphPlan& plan, const int32_t* k_knn, con
     return seeded;
 }
 
+// ---- initial poses (se3icp_register_graph_init, pose.hpp)
+// A VARIANT is a cloud under one initial pose: (cloud, the 128 bytes of the pose).  The unposed
+// variant of a cloud is the cloud itself; a pose that is bitwise the identity means "no pose".
+// Everything behind the ingest treats a variant as a cloud of its own: classes, tree orders and
+// seeds are planned over variants (GraphClass::cloud is then a variant).
+// se3icp_set_pose_seeding
+constexpr int kPoseSeedingMin = 0, kPoseSeedingMax = 1;
+enum InitStat : int { IS_EDGES = 0, IS_VARIANTS, IS_CROSS_SEEDED, IS_COUNT };
+struct VariantPlan {
+    std::vector<int32_t> edge_src, edge_tgt;  // [P]: the variant of an edge's source / target
+    std::vector<int32_t> cloud;               // [V]: its raw cloud
+    std::vector<int32_t> pose_edge;           // [V]: the first edge that carries its pose (-1: unposed)
+    int32_t posed_edges = 0, posed_variants = 0;
+};
+// Variants are numbered in order of first use (edge 0's source, edge 0's target, edge 1's
+// source, ...).  T_init: P row-major 4x4 poses, or null (no edge is posed).  Only a source is
+// ever posed; -0.0 is not +0.0, so a pose with a -0.0 where another has +0.0 is another variant.
+inline void graph_plan_variants(int32_t n_pairs, const int32_t* src, const int32_t* tgt, const double* T_init,
+                                VariantPlan* vp) {
+    static const double ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    struct Key {
+        int32_t cloud;
+        int32_t posed;
+        uint64_t b[16];
+        bool operator<(const Key& o) const {
+            if (cloud != o.cloud) return cloud < o.cloud;
+            if (posed != o.posed) return posed < o.posed;
+            return std::memcmp(b, o.b, sizeof(b)) < 0;
+        }
+    };
+    std::map<Key, int32_t> seen;
+    vp->edge_src.assign((size_t)n_pairs, -1);
+    vp->edge_tgt.assign((size_t)n_pairs, -1);
+    vp->cloud.clear();
+    vp->pose_edge.clear();
+    vp->posed_edges = vp->posed_variants = 0;
+    for (int32_t p = 0; p < n_pairs; ++p)
+        for (int side = 0; side < 2; ++side) {
+            Key k{};
+            k.cloud = side == 0 ? src[p] : tgt[p];
+            const double* M = (side == 0 && T_init) ? T_init + 16 * (size_t)p : nullptr;
+            if (M && std::memcmp(M, ident, sizeof(ident)) == 0) M = nullptr;
+            if (M) {
+                k.posed = 1;
+                std::memcpy(k.b, M, sizeof(k.b));
+                vp->posed_edges++;
+            }
+            auto it = seen.find(k);
+            int32_t id;
+            if (it == seen.end()) {
+                id = (int32_t)vp->cloud.size();
+                seen[k] = id;
+                vp->cloud.push_back(k.cloud);
+                vp->pose_edge.push_back(M ? p : -1);
+                vp->posed_variants += M ? 1 : 0;
+            } else {
+                id = it->second;
+            }
+            (side == 0 ? vp->edge_src : vp->edge_tgt)[p] = id;
+        }
+}
+
+// graph_plan_seeds for a plan over variants.  Under the run_se3_* normalization a rigid pose
+// preserves distances up to rounding, so the first selecting class of any rigid variant of a raw
+// cloud (the unposed one counts as rigid) seeds the later classes of every rigid variant of that
+// cloud; a variant whose pose is not rigid seeds within itself only, as does every variant with
+// cross = false (se3icp_set_pose_seeding(1)).  The conditions are graph_plan_seeds' except that
+// "centred with the same bits" is asked only between classes of one variant.
+// raw [variants]: the raw cloud of a variant; rigid [variants]: pose_is_rigid of its pose (nonzero
+// for the unposed variant).  *n_cross: the classes seeded from another variant's.  With every
+// variant unposed the result is graph_plan_seeds'.
+inline int32_t graph_plan_seeds_posed(const GraphPlan& plan, const int32_t* k_knn, const int64_t* n_pts,
+                                      const int32_t* raw, const int32_t* rigid, bool cross,
+                                      std::vector<SeedClass>* seed, int32_t* n_cross) {
+    const int32_t K = (int32_t)plan.classes.size();
+    seed->assign((size_t)K, SeedClass{-1, 1.0});
+    if (n_cross) *n_cross = 0;
+    if (!plan.normalize || !plan.dedupe) return 0;
+    auto uncentred = [](const GraphClass& g) { return g.f32_center[0] == 0.0 && g.f32_center[1] == 0.0 && g.f32_center[2] == 0.0; };
+    // (raw cloud, -1) for the rigid variants of a cloud together, (raw cloud, variant) otherwise
+    std::map<std::pair<int32_t, int32_t>, int32_t> source;
+    int32_t seeded = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        if (k_knn[k] <= 0) continue;
+        const GraphClass& g = plan.classes[k];
+        const int32_t v = g.cloud;
+        const std::pair<int32_t, int32_t> key{raw[v], (cross && rigid[v]) ? -1 : v};
+        auto it = source.find(key);
+        if (it == source.end()) {
+            source[key] = k;
+            continue;
+        }
+        const int32_t a = it->second;
+        const GraphClass& ga = plan.classes[a];
+        const int64_t kw = k_knn[k] < n_pts[k] ? k_knn[k] : n_pts[k], kwa = k_knn[a] < n_pts[a] ? k_knn[a] : n_pts[a];
+        const double rho = g.norm_scale / ga.norm_scale;
+        const bool same_variant = ga.cloud == v;
+        if ((same_variant && std::memcmp(g.norm_center, ga.norm_center, sizeof(g.norm_center)) != 0) || !uncentred(g) ||
+            !uncentred(ga) || n_pts[k] != n_pts[a] || kw > kwa || !(rho > 0.0) || !std::isfinite(rho * rho))
+            continue;
+        (*seed)[k] = SeedClass{a, rho * rho};
+        ++seeded;
+        if (!same_variant && n_cross) ++*n_cross;
+    }
+    return seeded;
+}
+
 // ---- one kd-tree order per cloud (build_trees, k_tree.hip)
 // The trees are implicit and balanced: node ranges come from the point count alone, every search
 // prunes on boxes computed from the points actually in a node, and no result depends on the

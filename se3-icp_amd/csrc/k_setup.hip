@@ -16,6 +16,7 @@
 #include <climits>
 
 #include "devmath.hpp"
+#include "pose.hpp"
 #include "view.hpp"
 
 namespace se3icp {
@@ -72,6 +73,53 @@ __global__ __launch_bounds__(256) void k_ingest(View v, const ChunkWork* chunks,
         v.xyz64[2 * v.ld + g] = z;
         v.cloud_of[g] = cw.cloud;
         if (st.want_conf) v.conf64[g] = lounge_conf(z);
+        acc[0] += x; acc[1] += y; acc[2] += z;
+        acc[3] = fmin(acc[3], x); acc[4] = fmin(acc[4], y); acc[5] = fmin(acc[5], z);
+        acc[6] = fmax(acc[6], x); acc[7] = fmax(acc[7], y); acc[8] = fmax(acc[8], z);
+    }
+    double s3[3] = {acc[0], acc[1], acc[2]};
+    double mn[3] = {acc[3], acc[4], acc[5]};
+    double mx[3] = {acc[6], acc[7], acc[8]};
+    block_reduce<3>(s3, OpAdd());
+    __syncthreads();
+    block_reduce<3>(mn, OpMin());
+    __syncthreads();
+    block_reduce<3>(mx, OpMax());
+    if (threadIdx.x == 0) {
+        double* o = partial + (size_t)blockIdx.x * 9;
+        o[0] = s3[0]; o[1] = s3[1]; o[2] = s3[2];
+        o[3] = mn[0]; o[4] = mn[1]; o[5] = mn[2];
+        o[6] = mx[0]; o[7] = mx[1]; o[8] = mx[2];
+    }
+}
+
+// k_ingest for a graph call with initial poses (Engine::register_graph): slot c is the raw cloud
+// read through apply_pose(poses + 16 * pose_of[c]) (pose.hpp: no FMA), or the raw cloud itself
+// where pose_of[c] < 0 -- then k_ingest's own statements.  The lounge confidences are a sensor
+// quantity and come from the raw z, before the pose.  A kernel of its own, so that k_ingest is
+// the code it was for every call without a pose.
+__global__ __launch_bounds__(256) void k_ingest_posed(View v, const ChunkWork* chunks, double* partial,
+                                                      const int32_t* pose_of, const double* poses) {
+    const ChunkWork cw = chunks[blockIdx.x];
+    const CloudDev cl = v.clouds[cw.cloud];
+    const CloudSetup st = v.setup[cw.cloud];
+    const double* in = v.in_ptr[cw.cloud];
+    const int pi = pose_of[cw.cloud];
+    double M[12];
+    for (int i = 0; i < 12; ++i) M[i] = pi >= 0 ? poses[16 * (size_t)pi + i] : 0.0;
+    double acc[9] = {0, 0, 0, DBL_MAX, DBL_MAX, DBL_MAX, -DBL_MAX, -DBL_MAX, -DBL_MAX};
+    const int end = min(cw.p0 + kChunk, cl.n);
+    for (int li = cw.p0 + threadIdx.x; li < end; li += blockDim.x) {
+        double q[3] = {in[3 * (size_t)li], in[3 * (size_t)li + 1], in[3 * (size_t)li + 2]};
+        const double zraw = q[2];
+        if (pi >= 0) apply_pose(M, q, q);
+        const double x = q[0], y = q[1], z = q[2];
+        const int g = cl.off + li;
+        v.xyz64[g] = x;
+        v.xyz64[v.ld + g] = y;
+        v.xyz64[2 * v.ld + g] = z;
+        v.cloud_of[g] = cw.cloud;
+        if (st.want_conf) v.conf64[g] = lounge_conf(zraw);
         acc[0] += x; acc[1] += y; acc[2] += z;
         acc[3] = fmin(acc[3], x); acc[4] = fmin(acc[4], y); acc[5] = fmin(acc[5], z);
         acc[6] = fmax(acc[6], x); acc[7] = fmax(acc[7], y); acc[8] = fmax(acc[8], z);
@@ -230,6 +278,11 @@ void launch_pair_norms(const View& v, int nnodes3, int nnodes12, const double* s
 }
 void launch_ingest(const View& v, const ChunkWork* chunks, int nchunks, double* partial, hipStream_t s) {
     if (nchunks > 0) hipLaunchKernelGGL(k_ingest, dim3(nchunks), dim3(256), 0, s, v, chunks, partial);
+}
+void launch_ingest_posed(const View& v, const ChunkWork* chunks, int nchunks, double* partial, const int32_t* pose_of,
+                         const double* poses, hipStream_t s) {
+    if (nchunks > 0)
+        hipLaunchKernelGGL(k_ingest_posed, dim3(nchunks), dim3(256), 0, s, v, chunks, partial, pose_of, poses);
 }
 void launch_radius(const View& v, const ChunkWork* chunks, int nchunks, const double* centers, double* partial,
                    hipStream_t s) {

@@ -116,6 +116,10 @@ constexpr int kChunk = 2048;
 struct ChunkWork { int32_t cloud; int32_t p0; };
 
 void launch_ingest(const View& v, const ChunkWork* chunks, int nchunks, double* partial /*[nchunks*9]*/, hipStream_t s);
+// launch_ingest for the slots of a graph call with initial poses: slot c is read through pose
+// pose_of[c] of `poses` (16 doubles each; pose_of[c] < 0: the raw cloud, as launch_ingest)
+void launch_ingest_posed(const View& v, const ChunkWork* chunks, int nchunks, double* partial /*[nchunks*9]*/,
+                         const int32_t* pose_of, const double* poses, hipStream_t s);
 void launch_radius(const View& v, const ChunkWork* chunks, int nchunks, const double* centers /*[nclouds*3]*/,
                    double* partial /*[nchunks]*/, hipStream_t s);
 void launch_normalize(const View& v, const ChunkWork* chunks, int nchunks, double* partial /*[nchunks*7]*/,

@@ -19,7 +19,8 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            register_graph_report, register_graph_traced, register_sequence, sequence_edges,
                            set_batch_sharing, set_lrf_seeding, last_seed_stats,
                            set_tree_sharing, last_tree_stats,
-                           voxel_downsample, voxel_downsample_device)
+                           voxel_downsample, voxel_downsample_device,
+                           edge_inits, last_init_stats, set_pose_seeding, transform_device, transform_points)
 from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
@@ -33,4 +34,5 @@ __all__ = [
     "register_graph_report", "register_graph_traced", "last_graph_stats",
     "set_batch_sharing", "set_lrf_seeding", "last_seed_stats", "set_tree_sharing", "last_tree_stats",
     "voxel_downsample", "voxel_downsample_device",
+    "edge_inits", "transform_points", "transform_device", "set_pose_seeding", "last_init_stats",
 ]

@@ -45,6 +45,9 @@ EXPORTED_SYMBOLS = [
     "se3icp_synthetic_pairs", "se3icp_synthetic_reference", "se3icp_synthetic_reference_device",
     "se3icp_random_downsample",
     "se3icp_voxel_version", "se3icp_voxel_downsample_device", "se3icp_voxel_downsample",
+    "se3icp_init_version", "se3icp_register_graph_init", "se3icp_register_graph_init_device",
+    "se3icp_set_initial_transform", "se3icp_set_pose_seeding", "se3icp_last_init_stats",
+    "se3icp_transform_points", "se3icp_transform_device",
     "se3icp_set_profiling", "se3icp_last_kernel_times", "se3icp_last_kernel_times_n", "se3icp_set_trace", "se3icp_set_lrf_exact",
     "se3icp_set_nn_events",
     # include/se3icp_cc.h: metrics and pose files of the benchmark drivers (host only)
@@ -138,6 +141,8 @@ GRAPH_STATS = ["clouds", "uses", "classes", "classes_full", "adopted", "rejected
                "bytes_uploaded"]
 # se3icp_last_seed_stats
 SEED_STATS = ["classes_seeded", "queries_seeded", "queries_unseeded", "queries_failed"]
+# se3icp_last_init_stats
+INIT_STATS = ["posed_edges", "posed_variants", "classes_seeded_across"]
 # se3icp_last_tree_stats
 TREE_STATS = ["built_3d", "adopted_3d", "built_12d", "adopted_12d"]
 
@@ -205,6 +210,19 @@ def load():
     L.se3icp_register_graph_report.argtypes = L.se3icp_register_graph.argtypes + [rop, rep]
     L.se3icp_register_graph_report_device.argtypes = L.se3icp_register_graph_device.argtypes + [rop, rep]
     L.se3icp_last_graph_stats.argtypes = [C.c_int, C.POINTER(C.c_int64), C.c_int]
+    if hasattr(L, "se3icp_init_version"):  # (SE3ICP_LIB may name an older build for an A/B run)
+        L.se3icp_init_version.restype = C.c_int
+        L.se3icp_register_graph_init.argtypes = [C.c_int, C.c_int32, C.POINTER(dp), C.POINTER(C.c_int64), C.c_int32,
+                                                 ip, ip, dp, C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(Result),
+                                                 rop, rep]
+        L.se3icp_register_graph_init_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), C.c_int32, ip, ip,
+                                                        dp, C.c_int, C.POINTER(Params), C.c_int32, C.POINTER(Result),
+                                                        vp, rop, rep]
+        L.se3icp_set_initial_transform.argtypes = [vp, dp]
+        L.se3icp_set_pose_seeding.argtypes = [C.c_int, C.c_int]
+        L.se3icp_last_init_stats.argtypes = [C.c_int, C.POINTER(C.c_int64), C.c_int]
+        L.se3icp_transform_points.argtypes = [dp, dp, C.c_int64, dp]
+        L.se3icp_transform_device.argtypes = [C.c_int, C.c_int32, vp, C.POINTER(C.c_int64), dp, vp, vp]
     L.se3icp_request_report.argtypes = [vp, rop]
     L.se3icp_get_report.argtypes = [vp, rep]
     L.se3icp_register.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.POINTER(Params),

@@ -91,6 +91,14 @@ class IterativeSE3Registration:
         pts = read_ply_xyz(cloud) if isinstance(cloud, (str, bytes)) else _as_xyz(cloud)
         _lib.check(self._L.se3icp_set_target_cloud(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)), pts.shape[0]))
 
+    def setInitialTransform(self, T):
+        """The pose (4x4, source frame -> target frame) every later run_* starts from
+        (se3icp_set_initial_transform): current_estimated_T_ is then the composed pose, as
+        Open3D's RegistrationICP(..., init) returns it.  None clears."""
+        M = None if T is None else _pose_array(T)
+        _lib.check(self._L.se3icp_set_initial_transform(self._h, None if M is None else M.ctypes.data_as(_DP)),
+                   "setInitialTransform")
+
     # ---- run methods (ISR.hpp:46-50)
     def _finish(self, rc):
         self._L.se3icp_get_result(self._h, C.byref(self._res))
@@ -269,8 +277,35 @@ def _registered(rc: int, what: str) -> None:
         raise _lib.Se3IcpError(rc, what)
 
 
-def register_batch(pairs, method: str, params: _lib.Params | None = None, device: int = 0) -> list[PairResult]:
-    """Register [(src (N,3), tgt (M,3)), ...] in lockstep on one GPU (host buffers)."""
+def _pose_array(T) -> np.ndarray:
+    M = np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+    if M.shape != (4, 4):
+        raise ValueError(f"expected a 4x4 pose, got shape {M.shape}")
+    return M
+
+
+def _init_array(init, n_edges: int):
+    """The T_init argument of the *_init entries: None (no edge is posed), or the (n_edges, 4, 4)
+    array of `init`, a sequence of 4x4 poses or Nones (None: the identity, "no pose")."""
+    if init is None:
+        return None
+    init = list(init)
+    if len(init) != n_edges:
+        raise ValueError(f"init has {len(init)} entries for {n_edges} edges")
+    if all(t is None for t in init):
+        return None
+    return np.ascontiguousarray(np.stack([np.eye(4) if t is None else _pose_array(t) for t in init]))
+
+
+def register_batch(pairs, method: str, params: _lib.Params | None = None, device: int = 0,
+                   init=None) -> list[PairResult]:
+    """Register [(src (N,3), tgt (M,3)), ...] in lockstep on one GPU (host buffers).  init: one
+    4x4 initial pose (or None) per pair; the call then goes through the graph entry with every
+    cloud distinct (register_graph(init=...))."""
+    if _init_array(init, len(pairs)) is not None:
+        clouds = [c for pair in pairs for c in pair]
+        return register_graph(clouds, [(2 * p, 2 * p + 1) for p in range(len(pairs))], method, params, device,
+                              init=init)
     n, args, _, _keep = _pair_args(pairs)
     res, _ = _outputs(n)
     _registered(_lib.load().se3icp_register_batch(device, n, *args, _lib.method_id(method), _params_ref(params), res),
@@ -658,38 +693,109 @@ def _edge_arrays(edges):
     return n, es, et
 
 
+def edge_inits(poses, edges) -> list[np.ndarray]:
+    """What a loop-closure caller passes as `init`: for absolute poses world_T_cloud (4x4 each) the
+    relative pose inv(P_t) @ P_s of every (s, t) of `edges`, with the rigid inverse
+    [R^T | -R^T t], in float64.  (A convenience: its arithmetic is not part of the bitwise
+    contract of register_graph(init=...), which starts at the poses it is handed.)"""
+    out = []
+    for s, t in edges:
+        Ps, Pt = _pose_array(poses[int(s)]), _pose_array(poses[int(t)])
+        inv = np.eye(4)
+        inv[:3, :3] = Pt[:3, :3].T
+        inv[:3, 3] = -(Pt[:3, :3].T @ Pt[:3, 3])
+        M = inv @ Ps
+        M[3] = (0.0, 0.0, 0.0, 1.0)
+        out.append(M)
+    return out
+
+
+def transform_points(T, xyz) -> np.ndarray:
+    """apply_pose(T, p) for every point of an (N, 3) array, on the host, in the engine's pinned
+    arithmetic (se3icp_transform_points): bitwise what register_graph(init=...) registers."""
+    pts, M = _as_xyz(xyz), _pose_array(T)
+    out = np.empty_like(pts)
+    _lib.check(_lib.load().se3icp_transform_points(M.ctypes.data_as(_DP), pts.ctypes.data_as(_DP), pts.shape[0],
+                                                   out.ctypes.data_as(_DP)), "transform_points")
+    return out
+
+
+def transform_device(xyz_ptr: int, off, poses, out_ptr: int | None = None, device: int = 0, stream: int = 0) -> None:
+    """One pose per cloud applied to clouds resident in HBM, all in one launch
+    (se3icp_transform_device): xyz_ptr / off as register_graph_device, poses n_clouds 4x4 arrays,
+    out_ptr a device buffer laid out as the input (None: in place)."""
+    nc = len(off) - 1
+    co = (C.c_int64 * (max(nc, 0) + 1))(*[int(x) for x in off])
+    M = np.ascontiguousarray(np.stack([_pose_array(t) for t in poses])) if nc > 0 else np.zeros((1, 4, 4))
+    if nc > 0 and M.shape[0] != nc:
+        raise ValueError(f"{M.shape[0]} poses for {nc} clouds")
+    _lib.check(_lib.load().se3icp_transform_device(int(device), nc, C.c_void_p(xyz_ptr), co, M.ctypes.data_as(_DP),
+                                                   C.c_void_p(xyz_ptr if out_ptr is None else out_ptr),
+                                                   _stream_arg(stream)), "transform_device")
+
+
+def set_pose_seeding(mode: int, device: int = 0) -> None:
+    """Whether the posed copies of a cloud seed each other's neighbour selection on the engine
+    behind `device` (se3icp_set_pose_seeding): 0 across poses (the default), 1 within one (cloud,
+    pose) only.  Results are bitwise the same; last_init_stats() describes the last call."""
+    _lib.check(_lib.load().se3icp_set_pose_seeding(int(device), int(mode)), "set_pose_seeding")
+
+
+def last_init_stats(device: int = 0) -> dict:
+    """Initial-pose counters of the last graph call on `device` (se3icp_last_init_stats)."""
+    out = (C.c_int64 * len(_lib.INIT_STATS))()
+    _lib.check(_lib.load().se3icp_last_init_stats(int(device), out, len(_lib.INIT_STATS)), "last_init_stats")
+    return {k: int(out[i]) for i, k in enumerate(_lib.INIT_STATS)}
+
+
 def register_graph(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
-                   sharing: int = 0, voxel_size: float | None = None) -> list[PairResult]:
+                   sharing: int = 0, voxel_size: float | None = None, init=None) -> list[PairResult]:
     """Register clouds[s] onto clouds[t] for every (s, t) of `edges`: result p is bitwise
     register_batch's for that pair, but every distinct cloud is uploaded and ingested once and
     set up once per normalization it takes part in (se3icp_register_graph).  sharing: 0 the
     engine's choice, 1 .. 3 see include/se3icp.h.  voxel_size: the clouds are raw scans; each is
     uploaded once, voxel-downsampled in HBM (voxel_downsample_device) and the result registered
-    by the device entry -- bitwise register_graph of the clouds voxel_downsample returns."""
+    by the device entry -- bitwise register_graph of the clouds voxel_downsample returns.
+    init: one 4x4 initial pose (source frame -> target frame) or None per edge
+    (se3icp_register_graph_init): result p is bitwise the plain call's for
+    (transform_points(init[p], source), target) except T, which is the composed pose."""
     if voxel_size is not None:
-        return _register_graph_voxel(clouds, edges, method, params, device, sharing, float(voxel_size))
+        return _register_graph_voxel(clouds, edges, method, params, device, sharing, float(voxel_size), init)
     _keep, cargs = _cloud_args(clouds)
     n, es, et = _edge_arrays(edges)
     res, _ = _outputs(n)
+    T0 = _init_array(init, n)
+    if T0 is not None:
+        _registered(_lib.load().se3icp_register_graph_init(device, *cargs, n, es, et, T0.ctypes.data_as(_DP),
+                                                           _lib.method_id(method), _params_ref(params), int(sharing),
+                                                           res, None, None), "register_graph_init")
+        return _results(res, n)
     _registered(_lib.load().se3icp_register_graph(device, *cargs, n, es, et, _lib.method_id(method), _params_ref(params),
                                                   int(sharing), res), "register_graph")
     return _results(res, n)
 
 
 def register_sequence(clouds, method: str, params: _lib.Params | None = None, device: int = 0,
-                      sharing: int = 0, voxel_size: float | None = None) -> list[PairResult]:
-    """register_graph over sequence_edges(len(clouds)): scan i+1 onto scan i."""
-    return register_graph(clouds, sequence_edges(len(clouds)), method, params, device, sharing, voxel_size)
+                      sharing: int = 0, voxel_size: float | None = None, init=None) -> list[PairResult]:
+    """register_graph over sequence_edges(len(clouds)): scan i+1 onto scan i (init: the odometry
+    prior of every step)."""
+    return register_graph(clouds, sequence_edges(len(clouds)), method, params, device, sharing, voxel_size, init)
 
 
 def register_graph_device(xyz_ptr: int, off, edges, method: str, params: _lib.Params | None = None,
-                          device: int = 0, stream: int = 0, sharing: int = 0) -> list[PairResult]:
+                          device: int = 0, stream: int = 0, sharing: int = 0, init=None) -> list[PairResult]:
     """register_graph for clouds already in HBM: xyz_ptr is the device address of the
     concatenated AoS float64 xyz of every cloud, off the n_clouds+1 point offsets."""
     nc = len(off) - 1
     co = (C.c_int64 * (nc + 1))(*[int(x) for x in off])
     n, es, et = _edge_arrays(edges)
     res, _ = _outputs(n)
+    T0 = _init_array(init, n)
+    if T0 is not None:
+        _registered(_lib.load().se3icp_register_graph_init_device(
+            device, nc, C.c_void_p(xyz_ptr), co, n, es, et, T0.ctypes.data_as(_DP), _lib.method_id(method),
+            _params_ref(params), int(sharing), res, _stream_arg(stream), None, None), "register_graph_init_device")
+        return _results(res, n)
     _registered(_lib.load().se3icp_register_graph_device(device, nc, C.c_void_p(xyz_ptr), co, n, es, et,
                                                          _lib.method_id(method), _params_ref(params), int(sharing),
                                                          res, _stream_arg(stream)), "register_graph_device")
@@ -697,13 +803,20 @@ def register_graph_device(xyz_ptr: int, off, edges, method: str, params: _lib.Pa
 
 
 def register_graph_report(clouds, edges, method: str, params: _lib.Params | None = None, device: int = 0,
-                          sharing: int = 0, max_correspondence_distance: float = 0.0, per_point: bool = False):
+                          sharing: int = 0, max_correspondence_distance: float = 0.0, per_point: bool = False,
+                          init=None):
     """register_graph plus a PairReport per edge, as register_batch_report: (results, reports)."""
     cl, cargs = _cloud_args(clouds)
     n, es, et = _edge_arrays(edges)
     counts = [cl[int(s)].shape[0] for s, _ in edges]
     res, rep = _outputs(n)
     opts, idx, dist = _per_point_options(max_correspondence_distance, counts, per_point)
+    T0 = _init_array(init, n)
+    if T0 is not None:
+        _registered(_lib.load().se3icp_register_graph_init(device, *cargs, n, es, et, T0.ctypes.data_as(_DP),
+                                                           _lib.method_id(method), _params_ref(params), int(sharing),
+                                                           res, C.byref(opts), rep), "register_graph_init")
+        return _results(res, n), _pair_reports(rep, counts, idx, dist)
     _registered(_lib.load().se3icp_register_graph_report(device, *cargs, n, es, et, _lib.method_id(method),
                                                          _params_ref(params), int(sharing), res, C.byref(opts), rep),
                 "register_graph_report")
@@ -711,10 +824,11 @@ def register_graph_report(clouds, edges, method: str, params: _lib.Params | None
 
 
 def register_graph_traced(clouds, edges, method: str, params: _lib.Params | None = None, edge: int = 0,
-                          max_iters: int = 160, device: int = 0, sharing: int = 0):
-    """register_graph with the per-iteration record of one edge (see register_batch_traced)."""
+                          max_iters: int = 160, device: int = 0, sharing: int = 0, init=None):
+    """register_graph with the per-iteration record of one edge (see register_batch_traced); with
+    init the record is the plain run's on the posed source."""
     with _armed_trace(device, edge, _as_xyz(clouds[int(edges[edge][0])]).shape[0], max_iters) as trace:
-        res = register_graph(clouds, edges, method, params, device, sharing)
+        res = register_graph(clouds, edges, method, params, device, sharing, init=init)
     return res, trace
 
 
@@ -761,7 +875,7 @@ def voxel_downsample_device(xyz_ptr: int, off, voxel_size, out_ptr: int, device:
     return [int(x) for x in oo]
 
 
-def _register_graph_voxel(clouds, edges, method, params, device, sharing, voxel_size):
+def _register_graph_voxel(clouds, edges, method, params, device, sharing, voxel_size, init=None):
     """register_graph(voxel_size=...): the raw clouds go to HBM once (torch holds the buffers),
     are downsampled there and registered where they lie."""
     import torch
@@ -775,7 +889,8 @@ def _register_graph_voxel(clouds, edges, method, params, device, sharing, voxel_
     down = torch.empty_like(raw)
     torch.cuda.synchronize(dev)  # the engine's stream is not torch's
     out_off = voxel_downsample_device(raw.data_ptr(), off, voxel_size, down.data_ptr(), device=device)
-    return register_graph_device(down.data_ptr(), out_off, edges, method, params, device=device, sharing=sharing)
+    return register_graph_device(down.data_ptr(), out_off, edges, method, params, device=device, sharing=sharing,
+                                 init=init)
 
 
 def last_graph_stats(device: int = 0) -> dict:

@@ -306,6 +306,30 @@ int se3icp_set_lrf_seeding(int device, int mode);
 #define SE3ICP_SEED_STATS_N 4
 int se3icp_last_seed_stats(int device, int64_t* out, int n);
 
+/* Taking.  With one kd-tree order per cloud (se3icp_set_tree_sharing, below) a local tree slot
+ * names the same point in every class of a cloud.  A seeded class whose selecting slot has its
+ * source's tree order, the same cloud and pose, and the same Kw = min(k, n) then takes the
+ * source's Kw neighbours of every point as a stored list instead of searching: it recomputes
+ * their exact keys under its own scale, puts them in its own order and certifies, from a lower
+ * bound the source stored of the distance of everything outside the list, that no other point
+ * can be as near as the list's farthest.  A wavefront that cannot certify all of its queries is
+ * redone as a seeded one, so a list costs time when it fails and never a result: results are
+ * bitwise the same in every mode.  A taking class counts as a class that ran a full selection
+ * in se3icp_last_graph_stats (whose adoption counters stay 0, reserved) and its taken queries
+ * count as seeded in se3icp_last_seed_stats.  Nothing takes with seeding modes 1-3, without tree
+ * sharing, across poses, under se3icp_set_lrf_exact, in the host-pointer batch entries or the
+ * sweeps.
+ * mode: 0 take (the default of every engine), 1 off, 2 every stored bound halved (a diagnostic:
+ * every wavefront is redone).  Anything else is SE3ICP_ERR_INVALID_ARG, checked before the
+ * device is looked up.  The setting is the engine's (device | slot << 8). */
+int se3icp_set_lrf_taking(int device, int mode);
+/* Of the last registration call on `device`: out[SE3ICP_TAKE_STATS_N], n >= that (else
+ * SE3ICP_ERR_INVALID_ARG) = {classes taking, queries that took their list, queries of redone
+ * wavefronts, queries whose stored list failed the order check or the certificate}.  A query the
+ * source handed to the exact kernel has no list: its wavefront is redone and nothing failed. */
+#define SE3ICP_TAKE_STATS_N 4
+int se3icp_last_take_stats(int device, int64_t* out, int n);
+
 /* One kd-tree order per cloud.  The trees are implicit and balanced, their node ranges come
  * from the point count alone and every search prunes on boxes computed from the points that
  * are in a node, so any order with correct boxes is a valid tree and no result depends on it.

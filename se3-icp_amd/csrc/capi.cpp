@@ -470,6 +470,24 @@ int se3icp_last_seed_stats(int device, int64_t* out, int n) {
     return SE3ICP_OK;
 }
 
+int se3icp_set_lrf_taking(int device, int mode) {
+    if (mode < se3icp::kLrfTakingMin || mode > se3icp::kLrfTakingMax) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_lrf_taking(mode);
+    return SE3ICP_OK;
+}
+
+int se3icp_last_take_stats(int device, int64_t* out, int n) {
+    if (!out || n < se3icp::TS_COUNT) return SE3ICP_ERR_INVALID_ARG;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    for (int k = 0; k < se3icp::TS_COUNT; ++k) out[k] = e->take_stats()[k];
+    return SE3ICP_OK;
+}
+
 int se3icp_set_tree_sharing(int device, int mode) {
     if (mode < se3icp::kTreeSharingMin || mode > se3icp::kTreeSharingMax) return SE3ICP_ERR_INVALID_ARG;
     Engine* e = usable_engine(device);

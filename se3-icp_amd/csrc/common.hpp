@@ -28,6 +28,10 @@ constexpr int kStatUseSe3 = 15, kStatUseR3 = 16;
 // clouds counts in columns kSeedStatCol .. + 2 the queries of waves that started from a seed,
 // that ran without one (an absent seed; a wave the exact kernel takes whole), whose seed failed
 constexpr int kSeedStatCol = 14;
+// ... and of taking clouds in column kTakeStatCol the queries that took their source's list, in
+// the next the queries of redone waves (low 32 bits) and the queries that failed the order check
+// or the certificate (high 32 bits)
+constexpr int kTakeStatCol = 12;
 constexpr int kHist = 256;        // pose history ring of the loop (View::hist), iterations
 constexpr int kTrimList = 4096;   // k_trim: LDS key list / window capacity per pair
 constexpr int kTrimBlocks = 32;   // k_trim_window: blocks per pair

@@ -521,33 +521,57 @@ int Engine::setup_knn(hipStream_t s) {
             // waves aligned to each cloud's first point (results independent of the batch)
             // Two wave tables: the seeded clouds of select_by_class (graph.hpp, graph_plan_seeds)
             // run in a launch of their own behind the one that stores their seeds.
-            const bool seeding = seed_on_;
+            // The taking clouds among them (graph_plan_takes) have a third table: a launch that
+            // takes the lists the first one stored, then a seeded launch over the same table for
+            // the waves that could not (sources, take, redo in stream order).
+            const bool seeding = seed_on_, taking = seed_on_ && take_on_;
             const int nt = nclouds_ + 1;
-            std::vector<int32_t> wb(2 * (size_t)nt, 0);
+            std::vector<int32_t> wb(3 * (size_t)nt, 0);
             // (a cloud that wants no neighbours gets no waves: the kernel's search for a wave's
             // cloud takes the last one that starts at or before it)
             for (int c = 0; c < nclouds_; ++c) {
                 const int waves = h_setup_[c].k_knn > 0 ? (h_clouds_[c].n + 7) / 8 : 0;
                 const bool sd = seeding && seed_ref_[c].load >= 0;
+                const bool tk = sd && taking && (take_flag_[c] & 2);
                 wb[c + 1] = wb[c] + (sd ? 0 : waves);
-                wb[nt + c + 1] = wb[nt + c] + (sd ? waves : 0);
+                wb[nt + c + 1] = wb[nt + c] + (sd && !tk ? waves : 0);
+                wb[2 * nt + c + 1] = wb[2 * nt + c] + (tk ? waves : 0);
             }
-            const int nw = wb[nclouds_], nw_sd = wb[nt + nclouds_];
-            if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * (nw + nw_sd) + 64) || !ensure<int32_t>(d_lrf_fbn_, 2 + 2 * (size_t)nt))
+            const int nw = wb[nclouds_], nw_sd = wb[nt + nclouds_], nw_tk = wb[2 * nt + nclouds_];
+            if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * ((size_t)nw + nw_sd + nw_tk) + 64) ||
+                !ensure<int32_t>(d_lrf_fbn_, 2 + 3 * (size_t)nt))
                 return SE3ICP_ERR_OUT_OF_MEMORY;
             int32_t* d_wb = (int32_t*)d_lrf_fbn_.p + 2;
             int32_t* fb = (int32_t*)d_lrf_fb_.p;
             int32_t* fbn = (int32_t*)d_lrf_fbn_.p;
             HIPCHK(hipMemsetAsync(fbn, 0, 2 * sizeof(int32_t), s));
-            HIPCHK(hipMemcpyAsync(d_wb, wb.data(), sizeof(int32_t) * 2 * nt, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_wb, wb.data(), sizeof(int32_t) * 3 * nt, hipMemcpyHostToDevice, s));
             if (seeding) {
-                if (!ensure<float>(d_seed_, (size_t)seed_floats_) || !ensure<SeedRef>(d_seed_ref_, nclouds_))
+                // (with taking the bounds Lb follow the seeds: one fill marks both absent)
+                const size_t nseed = (size_t)seed_floats_ * (taking ? 2 : 1);
+                if (!ensure<float>(d_seed_, nseed) || !ensure<SeedRef>(d_seed_ref_, nclouds_))
                     return SE3ICP_ERR_OUT_OF_MEMORY;
-                HIPCHK(hipMemsetAsync(d_seed_.p, 0xff, sizeof(float) * (size_t)seed_floats_, s));  // all ones: absent
+                HIPCHK(hipMemsetAsync(d_seed_.p, 0xff, sizeof(float) * nseed, s));  // all ones: absent
                 HIPCHK(hipMemcpyAsync(d_seed_ref_.p, seed_ref_.data(), sizeof(SeedRef) * nclouds_, hipMemcpyHostToDevice, s));
-                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s, (const SeedRef*)d_seed_ref_.p, (float*)d_seed_.p, false, lrf_seeding_);
-                launch_lrf8(v, d_wb + nt, 0, nw_sd, fb, fbn, s, (const SeedRef*)d_seed_ref_.p, (float*)d_seed_.p, true,
-                            lrf_seeding_);
+                const SeedRef* sref = (const SeedRef*)d_seed_ref_.p;
+                float* sbuf = (float*)d_seed_.p;
+                TakeArgs tk{nullptr, nullptr, nullptr, 0, 0, 0};
+                if (taking && nw_tk > 0) {
+                    if (!ensure<uint32_t>(d_take_lists_, (size_t)seed_floats_ * (size_t)take_stride_) ||
+                        !ensure<int32_t>(d_take_flag_, nclouds_) || !ensure<unsigned char>(d_take_mask_, (size_t)nw_tk + 64))
+                        return SE3ICP_ERR_OUT_OF_MEMORY;
+                    HIPCHK(hipMemcpyAsync(d_take_flag_.p, take_flag_.data(), sizeof(int32_t) * nclouds_, hipMemcpyHostToDevice, s));
+                    HIPCHK(hipMemsetAsync(d_take_mask_.p, 0, (size_t)nw_tk + 64, s));
+                    tk = TakeArgs{(const int32_t*)d_take_flag_.p, (uint32_t*)d_take_lists_.p, nullptr, take_stride_,
+                                  (int32_t)seed_floats_, lrf_taking_};
+                }
+                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s, sref, sbuf, false, lrf_seeding_, &tk);
+                launch_lrf8(v, d_wb + nt, 0, nw_sd, fb, fbn, s, sref, sbuf, true, lrf_seeding_);
+                if (tk.flag != nullptr) {
+                    tk.mask = (unsigned char*)d_take_mask_.p;
+                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, lrf_seeding_, &tk, true);
+                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, lrf_seeding_, &tk);
+                }
             } else {
                 launch_lrf8(v, d_wb, 0, nw, fb, fbn, s);
             }
@@ -585,6 +609,17 @@ int Engine::read_lrf_stats() {
         unsigned long long q = 0;
         for (int i = 0; i < kStatSlots; ++i) q += h_lrf_stats_[kStatCols * i + kSeedStatCol + k];
         seed_stats_[1 + k] = (int64_t)q;
+    }
+    {  // ... and of taking clouds (kTakeStatCol: taken; redone | failed << 32)
+        unsigned long long t = 0, r = 0, f = 0;
+        for (int i = 0; i < kStatSlots; ++i) {
+            t += h_lrf_stats_[kStatCols * i + kTakeStatCol];
+            r += h_lrf_stats_[kStatCols * i + kTakeStatCol + 1] & 0xffffffffull;
+            f += h_lrf_stats_[kStatCols * i + kTakeStatCol + 1] >> 32;
+        }
+        take_stats_[TS_TAKEN] = (int64_t)t;
+        take_stats_[TS_REDONE] = (int64_t)r;
+        take_stats_[TS_FAILED] = (int64_t)f;
     }
 #ifdef SE3ICP_PROF
     tree_prof_report();
@@ -643,6 +678,7 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     c->s = user_stream ? user_stream : stream_;
     ktimes_ = KernelTimes{};
     for (int64_t& x : seed_stats_) x = 0;
+    for (int64_t& x : take_stats_) x = 0;
     for (int64_t& x : tree_stats_) x = 0;
     tree_donor_.clear();
     // phase times on the GPU timeline (the host does not wait for the setup): events
@@ -909,12 +945,38 @@ int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>
             seed_stats_[0] = seeded;
             init_stats_[IS_CROSS_SEEDED] = cross;
             seed_on_ = true;
+            // taking: a seeded class with its source's tree order takes the source's lists
+            // (graph_plan_takes); only with both switches at their defaults (taking mode 2 is
+            // the default with every bound halved)
+            take_flag_.clear();
+            take_stride_ = 0;
+            if (lrf_seeding_ == 0 && lrf_taking_ != 1 && (int)tree_donor_.size() == U) {
+                std::vector<uint8_t> tk;
+                const int taking = graph_plan_takes(plan, sc, kk.data(), nn.data(), home.data(), tree_donor_, &tk);
+                int64_t kw_max = 0;
+                for (int k = 0; k < K; ++k)
+                    if (tk[k]) kw_max = std::max<int64_t>(kw_max, std::min<int64_t>(kk[k], nn[k]));
+                // (lists of Kw <= 128 entries, 16-B aligned; longer ones are never taken)
+                const int64_t stride = (std::min<int64_t>(kw_max, kSmallK) + 3) & ~(int64_t)3;
+                if (taking > 0 && 2 * seed_floats_ <= INT32_MAX) {
+                    take_flag_.assign(U, 0);
+                    for (int k = 0; k < K; ++k) {
+                        if (!tk[k]) continue;
+                        take_flag_[home[k]] |= 2;
+                        take_flag_[home[sc[k].from]] |= 1;
+                    }
+                    take_stride_ = (int)stride;
+                    take_stats_[TS_CLASSES] = taking;
+                    take_on_ = true;
+                }
+            }
         }
     }
     h_setup_ = sel_run_;
     HIPCHK(hipMemcpyAsync(d_setup_.p, sel_run_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
     const int rc = setup_knn(s);
     seed_on_ = false;  // (seed_ref_ itself stays: the copy that reads it may still be queued)
+    take_on_ = false;  // (as does take_flag_)
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     // the batch's own table from here on (the copies below read cf_target of the use itself)

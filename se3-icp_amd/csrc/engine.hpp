@@ -95,6 +95,7 @@ class Engine {
     void set_batch_sharing(int level) { batch_sharing_ = level; }
     void set_lrf_seeding(int mode) { lrf_seeding_ = mode; }
     void set_tree_sharing(int mode) { tree_sharing_ = mode; }
+    void set_lrf_taking(int mode) { lrf_taking_ = mode; }
     const KernelTimes& kernel_times() const { return ktimes_; }
 
     int register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
@@ -135,6 +136,10 @@ class Engine {
     // waves that started from a seed, that ran without one, that were handed over after a
     // failed certificate
     const int64_t* seed_stats() const { return seed_stats_; }
+    // [TS_COUNT] of the last registration call (se3icp_last_take_stats): classes taking, queries
+    // that took their source's list, queries of redone waves, queries that failed the order check
+    // or the certificate
+    const int64_t* take_stats() const { return take_stats_; }
     // [4] of the last registration call (se3icp_last_tree_stats): 3-D trees built / adopted,
     // 12-D trees built / adopted
     const int64_t* tree_stats() const { return tree_stats_; }
@@ -333,6 +338,17 @@ class Engine {
     int64_t seed_floats_ = 0;
     DevBuf d_seed_{bufs_}, d_seed_ref_{bufs_};
     int64_t seed_stats_[4] = {};
+    // se3icp_set_lrf_taking: 0 a seeded class with its source's tree order takes the source's
+    // neighbour lists (default), 1 off, 2 a diagnostic: every stored bound halved, every wave redone
+    int lrf_taking_ = 0;
+    // select_by_class -> setup_knn: whether this selection takes, bit 0 (stores lists) / bit 1
+    // (takes) of every use, the entries per list, and the lists, flags and redo mask on the device
+    // (the bounds Lb follow the seeds in d_seed_)
+    bool take_on_ = false;
+    std::vector<int32_t> take_flag_;
+    int take_stride_ = 0;
+    DevBuf d_take_lists_{bufs_}, d_take_flag_{bufs_}, d_take_mask_{bufs_};
+    int64_t take_stats_[TS_COUNT] = {};
     // graph_plan_trees of the call: per slot -1 or the slot whose tree order it adopts.  Set by
     // setup_pairs_shared and register_graph, read by run_pairs for the 12-D trees, cleared by
     // open_call (a call that shares nothing has no donors).  The tables of the call's builds:

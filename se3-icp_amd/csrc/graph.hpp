@@ -185,6 +185,41 @@ inline int32_t graph_plan_seeds(const GraphPlan& plan, const int32_t* k_knn, con
     return seeded;
 }
 
+// ---- taking the source's neighbour lists
+// A seeded class whose selecting slot has the 3-D tree order of its source's selecting slot names
+// every point by the same local tree slot, so it can take the source's Kw neighbours as a list
+// and only re-check them under its own scale.  se3icp_set_lrf_taking
+constexpr int kLrfTakingMin = 0, kLrfTakingMax = 2;
+enum TakeStat : int { TS_CLASSES = 0, TS_TAKEN, TS_REDONE, TS_FAILED, TS_COUNT };
+// seed [classes]: graph_plan_seeds' (or graph_plan_seeds_posed's) result; k_knn, n_pts as there;
+// home [classes]: the slot that selects for the class; donor: graph_plan_trees' table over the
+// slots (empty: no slot adopted an order).  take[k] != 0: class k takes from seed[k].from.  It
+// does when it is seeded, is a class of the same cloud (variant) as its source, asks for exactly
+// as many neighbours, Kw = min(k_knn, n), and both home slots are the builder or adopters of one
+// donor group.  Returns the taking classes.
+inline int32_t graph_plan_takes(const GraphPlan& plan, const std::vector<SeedClass>& seed, const int32_t* k_knn,
+                                const int64_t* n_pts, const int32_t* home, const std::vector<int32_t>& donor,
+                                std::vector<uint8_t>* take) {
+    const int32_t K = (int32_t)plan.classes.size();
+    take->assign((size_t)K, 0);
+    if (!plan.normalize || !plan.dedupe || (int32_t)seed.size() != K || donor.empty()) return 0;
+    const int32_t U = (int32_t)donor.size();
+    auto group = [&](int32_t u) { return (u < 0 || u >= U) ? -1 : (donor[u] >= 0 ? donor[u] : u); };
+    int32_t taking = 0;
+    for (int32_t k = 0; k < K; ++k) {
+        const int32_t a = seed[k].from;
+        if (a < 0 || a >= K || a == k) continue;
+        const int64_t kw = k_knn[k] < n_pts[k] ? k_knn[k] : n_pts[k], kwa = k_knn[a] < n_pts[a] ? k_knn[a] : n_pts[a];
+        const int32_t gk = group(home[k]), ga = group(home[a]);
+        if (plan.classes[k].cloud != plan.classes[a].cloud || n_pts[k] != n_pts[a] || kw != kwa || kw <= 0 || gk < 0 ||
+            gk != ga)
+            continue;
+        (*take)[k] = 1;
+        ++taking;
+    }
+    return taking;
+}
+
 // ---- initial poses (se3icp_register_graph_init, pose.hpp)
 // A VARIANT is a cloud under one initial pose: (cloud, the 128 bytes of the pose).  The unposed
 // variant of a cloud is the cloud itself; a pose that is bitwise the identity means "no pose".

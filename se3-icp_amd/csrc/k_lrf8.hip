@@ -33,6 +33,7 @@
 
 #include "devmath.hpp"
 #include "knn_util.hpp"
+#include "lrf_bounds.hpp"
 #include "tree.hpp"
 #include "view.hpp"
 #include "wave.hpp"
@@ -69,10 +70,8 @@ constexpr int kFill = SE3ICP_LRF8_FILL;
 constexpr int kStride = kCap + 4;
 static_assert(((kStride / 4) & 1) == 1, "an odd number of 16-B slots per list");
 constexpr int kLeaves = 64;              // leaves one wave may scan: candidate id = (list index << 6) | lane
-constexpr unsigned kIdBits = 0xfffu;     // low bits of a list entry: the candidate id
-// bound of the accept-all phase: every finite key (a lane past the leaf's end carries an
-// infinite distance, so its entry is above every bound)
-constexpr unsigned kAll = 0x7f7fffffu;
+// (kIdBits, the low bits of a list entry: the candidate id, and kAll, the bound of the accept-all
+// phase: lrf_bounds.hpp, with f32_err3 and widen_bound)
 constexpr unsigned kPad = 0xffffffffu;   // sort padding (> every entry)
 
 // park slots per query (doubles)
@@ -226,20 +225,6 @@ __device__ __forceinline__ void sort_run(unsigned* list, int len, int l) {
     }
     __builtin_amdgcn_wave_barrier();
 }
-// |f32 squared distance of the f32-rounded points - exact squared distance of the f64
-// points| for distances <= d (loopdev.hpp f32_err, D = 3); S bounds the sum of the norms
-__device__ __forceinline__ float f32_err3(float d, float S) {
-    const float u = 5.9604645e-08f;
-    return 1.25f * (2.f * u * S * sqrtf(fmaxf(d, 0.f)) + 6.f * u * d + 4.f * u * u * S * S) + 1e-30f;
-}
-// the list bound from the Kw-th smallest entry t (f32 keys): every point whose exact
-// distance is within the Kw-th smallest exact distance has an f32 key <= the value of t
-// plus two errors
-__device__ __forceinline__ unsigned widen_bound(unsigned t, float S) {
-    if (t >= 0x7f800000u) return kAll;
-    const float b = __uint_as_float(t);
-    return min((__float_as_uint(fmaf(2.02f, f32_err3(b, S), b)) + 2u) | kIdBits, kAll);
-}
 // number of entries <= t in the sorted run A[0 .. n)
 __device__ __forceinline__ int upper_count(const unsigned* A, int n, unsigned t) {
     int lo = 0, hi = n;
@@ -342,54 +327,25 @@ __device__ __forceinline__ p3 ld3(const double4* __restrict__ P4, int i) {
 // swap when no neighbouring rank shares their key.  Returns false (the query goes to the
 // exact kernel) when the order is still wrong, or when a run of three or more ranks shares
 // an f32 key and is not already in the exact order.
-__device__ __forceinline__ bool final_group(unsigned* lists, const int* leaf_slot, const double4* __restrict__ P4,
+//
+// final_exact is that exact back end: slot[s] is the tree slot of entry l * 16 + s (< nbg) of
+// the order to put right -- final_group's u32 order, or a list taken from another class of the
+// cloud; bad0 fails the lane's query beforehand.
+__device__ __forceinline__ bool final_exact(unsigned* list, const int (&slot)[16], bool bad0, const double4* __restrict__ P4,
                                             const int32_t* __restrict__ perm, double qx, double qy, double qz, int off,
-                                            int g, int l, int nbg, int mv, int fmode, int lim) {
-    unsigned* list = lists + g * kStride;
+                                            int g, int l, int nbg, int lim) {
     unsigned long long k[16];
-    bool unsorted = false;
-    {
-        unsigned k32[16];
-        // fmode (wave-uniform): 0 a full sort; 1 the sorted prefix list[0 .. mv) (the last
-        // tightening's kept set) merged with the tail appended since (<= 64 entries, sorted
-        // first), as tighten_group_sorted merges; 2 the tail is empty (already in order)
-        if (fmode == 0) {
-            load_head<16>(list, nbg, l, k32);
-            sort8<16>(k32, l);
-        } else {
-            const int nb = nbg - mv;
-            unsigned* B = list + mv;
-            if (fmode == 1) sort_run<8>(B, nb, l);
-            load_head<16>(list, mv, l, k32);
-            if (fmode == 1) {
+    bool unsorted = bad0;
 #pragma unroll
-                for (int s = 0; s < 16; ++s) {
-                    const int e = l * 16 + s;
-                    if (e >= 128 - nb) k32[s] = B[127 - e];
-                }
-                __builtin_amdgcn_wave_barrier();
-                stage8<16, 128, 64>(k32, l);
-                stage8<16, 128, 32>(k32, l);
-                stage8<16, 128, 16>(k32, l);
-                stage8<16, 128, 8>(k32, l);
-                stage8<16, 128, 4>(k32, l);
-                stage8<16, 128, 2>(k32, l);
-                stage8<16, 128, 1>(k32, l);
-            }
+    for (int s = 0; s < 16; ++s) {
+        const int e = l * 16 + s;
+        unsigned long long x = ~0ull;
+        if (e < nbg) {
+            const p3 p = ld3(P4, slot[s]);
+            const unsigned key = __float_as_uint((float)l2_3(qx, qy, qz, p.x, p.y, p.z));
+            x = ((unsigned long long)key << 32) | (unsigned)(slot[s] - off);
         }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int e = l * 16 + s;
-            unsigned long long x = ~0ull;
-            if (e < nbg) {
-                const unsigned id = k32[s] & kIdBits;
-                const int slot = leaf_slot[id >> 6] + (int)(id & 63u);
-                const p3 p = ld3(P4, slot);
-                const unsigned key = __float_as_uint((float)l2_3(qx, qy, qz, p.x, p.y, p.z));
-                x = ((unsigned long long)key << 32) | (unsigned)(slot - off);
-            }
-            k[s] = x;
-        }
+        k[s] = x;
     }
     auto ce = [](unsigned long long& a, unsigned long long& b) __attribute__((always_inline)) {
         const bool sw = b < a;
@@ -477,6 +433,51 @@ __device__ __forceinline__ bool final_group(unsigned* lists, const int* leaf_slo
     return ok;
 }
 
+// final_group: the u32 front end, then final_exact
+__device__ __forceinline__ bool final_group(unsigned* lists, const int* leaf_slot, const double4* __restrict__ P4,
+                                            const int32_t* __restrict__ perm, double qx, double qy, double qz, int off,
+                                            int g, int l, int nbg, int mv, int fmode, int lim) {
+    unsigned* list = lists + g * kStride;
+    {
+        unsigned k32[16];
+        // fmode (wave-uniform): 0 a full sort; 1 the sorted prefix list[0 .. mv) (the last
+        // tightening's kept set) merged with the tail appended since (<= 64 entries, sorted
+        // first), as tighten_group_sorted merges; 2 the tail is empty (already in order)
+        if (fmode == 0) {
+            load_head<16>(list, nbg, l, k32);
+            sort8<16>(k32, l);
+        } else {
+            const int nb = nbg - mv;
+            unsigned* B = list + mv;
+            if (fmode == 1) sort_run<8>(B, nb, l);
+            load_head<16>(list, mv, l, k32);
+            if (fmode == 1) {
+#pragma unroll
+                for (int s = 0; s < 16; ++s) {
+                    const int e = l * 16 + s;
+                    if (e >= 128 - nb) k32[s] = B[127 - e];
+                }
+                __builtin_amdgcn_wave_barrier();
+                stage8<16, 128, 64>(k32, l);
+                stage8<16, 128, 32>(k32, l);
+                stage8<16, 128, 16>(k32, l);
+                stage8<16, 128, 8>(k32, l);
+                stage8<16, 128, 4>(k32, l);
+                stage8<16, 128, 2>(k32, l);
+                stage8<16, 128, 1>(k32, l);
+            }
+        }
+        // the tree slot of each entry (its leaf's first slot + its lane in the leaf)
+        int slot[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const unsigned id = k32[s] & kIdBits;
+            slot[s] = l * 16 + s < nbg ? leaf_slot[id >> 6] + (int)(id & 63u) : 0;
+        }
+        return final_exact(list, slot, false, P4, perm, qx, qy, qz, off, g, l, nbg, lim);
+    }
+}
+
 // SE3ICP_PROF builds (make prof): per-section shader-clock cycles into stats columns 8..11
 #ifdef SE3ICP_PROF
 #define PROF8_NOW(t) const unsigned long long t = __builtin_readcyclecounter()
@@ -501,13 +502,24 @@ static_assert(kW >= 2 && kW * kQ <= 64, "the per-block epilogue: waves 0 and 1, 
 // queries go to the exact kernel.  The seed is a hint: it costs time when wrong, never a result.
 //
 // waves per SIMD: 6 = the LDS limit (26.6 KB per block); A/B 4 -> 5 -> 6: 6.73 -> 6.45 -> 6.38 ms
-template <bool SD, bool ST>
+//
+// Taking.  A storing wave (ST, tk.flag[c] & 1) also writes every kept
+// query's Kw tree slots in rank order and a lower bound Lb of the distance of every point outside
+// them.  TK = true, a launch of taking clouds only: a wave reads the eight lists and bounds its
+// source stored -- the two classes share one tree order, so a local tree slot is the same point in
+// both -- puts them in its own exact order (final_exact) and certifies each against Lb
+// (take_bound); it then runs the sums and the epilogue as every wave does.  A wave that cannot
+// (an absent Lb, a failed order or certificate, a slot out of range, a partial wave, Kw > 128)
+// writes and counts nothing and sets its byte of tk.mask, and the SD launch behind it, which
+// skips the waves whose byte is 0, runs it as a seeded wave.
+template <bool SD, bool ST, bool TK = false>
 __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <= 192 ? 6 : (kCap <= 224 ? 5 : 4)))) void k_lrf8(
     View v, const int32_t* __restrict__ cloud_of, const CloudSetup* __restrict__ setup,
     const CloudDev* __restrict__ clouds, const float* __restrict__ tlo, const float* __restrict__ thi,
     const double4* __restrict__ P4, const int32_t* __restrict__ wave_base, int w_lo, int nwaves,
     int32_t* __restrict__ fb_list, int32_t* __restrict__ fb_count, const SeedRef* __restrict__ seed,
-    float* __restrict__ seedbuf, int seed_mode) {
+    float* __restrict__ seedbuf, int seed_mode, TakeArgs tk) {
+    static_assert(!TK || (SD && !ST), "a taking launch is a launch of seeded clouds");
     // (a query's park overlays the tail of its list, free once the list is final: <= 128 entries)
     __shared__ __attribute__((aligned(16))) unsigned s_list[kW][kQ][kStride];
     auto park_of = [&](int w, int j) __attribute__((always_inline)) {
@@ -543,7 +555,20 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
     CloudSetup st{};
     CloudDev cl{0, 0};
     int K = 0, Kw = 0;
-    if (wv < nwaves) {
+    bool redo_skip = false;  // the launch behind a taking one: a wave that took has nothing to do
+    if constexpr (SD && !TK) {
+        if (tk.mask != nullptr) {
+            unsigned any = 0u;  // (block-uniform: a block none of whose waves is redone ends here)
+#pragma unroll
+            for (int j = 0; j < kW; ++j) {
+                const int wj = w_lo + bid * kW + j;
+                any |= wj < nwaves ? (unsigned)tk.mask[wj] : 0u;
+            }
+            if (any == 0u) return;
+            redo_skip = wv < nwaves && tk.mask[wv] == 0;
+        }
+    }
+    if (wv < nwaves && !redo_skip) {
         int lo = 0, hi = v.nclouds - 1;  // last cloud with wave_base <= wv
         while (lo < hi) {
             const int mid = (lo + hi + 1) >> 1;
@@ -615,7 +640,9 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
     // t_cert: the last tightening's bounds all came out at or below the bounds before it
     bool sd_open = false, sd_close = false, t_cert = true;
     unsigned n_sdq = 0, n_sda = 0, n_sdf = 0;
-    if constexpr (SD) {
+    unsigned n_tkq = 0, n_tkr = 0, n_tkf = 0;  // queries taken, redone, failed in the order or the certificate
+    if constexpr (SD && !TK) {
+        if (tk.mask != nullptr) n_tkr = (unsigned)qn;
         if (mode == 2) n_sda = (unsigned)qn;
         if (mode == 1) {
             const SeedRef sr = seed[c];
@@ -751,7 +778,7 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
         return true;
     };
 
-    if (mode == 1) {
+    if (!TK && mode == 1) {
         // The leaves holding the eight queries, then their tree-order neighbours, every
         // point accepted, until each query has Kw candidates: the first bound.
         const int lf0 = tree_node_of(w0 - cl.off, n, T.L), lf1 = tree_node_of(w0 + kQ - 1 - cl.off, n, T.L);
@@ -925,15 +952,71 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
     // be strict (else the query goes to the exact kernel).
     const int kl = st.k_lrf, kn_want = st.k_nrm;
     const bool want_t = kl > 0, want_n = kn_want > 0;
+    if constexpr (TK) {
+        if (mode == 2) {  // (a partial wave, Kw > 128: redone)
+            if (lane == 0) tk.mask[wv] = 1;
+            mode = 0;
+            fb_wave = false;
+        }
+    }
     bool fb_q = fb_wave;  // (group-uniform)
-    const int nbg = (int)group_len();
+    const int nbg = TK ? (mode == 1 ? Kw : 0) : (int)group_len();  // (a taken list has Kw entries)
     const int nTop = min(Kw, nbg);
     const int kk = min(kl, nTop), kn = min(kn_want, nTop);
     const int wq = w0 + g;
     // the group's f64 query (final order, sums)
     p3 qg{0.0, 0.0, 0.0};
     if (mode == 1) qg = ld3(P4, wq);
-    if (mode == 1 && !fb_wave) {
+    if constexpr (TK) {
+        if (mode == 1) {
+            // the list and the bound the source stored for this local tree slot
+            const SeedRef sr = seed[c];
+            const size_t at = (size_t)sr.load + (size_t)(wq - cl.off);
+            float lb = seedbuf[(size_t)tk.lb_off + at];
+            if (tk.mode == 2) lb *= 0.5f;
+            // (an absent bound is all ones, a NaN)
+            const bool absent = !(bool)((int)(lb >= 0.f) & (int)(lb < INFINITY));
+            bool bad = absent;
+            const unsigned* src = tk.lists + at * (size_t)tk.stride;
+            int slot[16];
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int e0 = l * 16 + 4 * q4;
+                uint4 x = make_uint4(0u, 0u, 0u, 0u);
+                if (e0 < Kw) x = *reinterpret_cast<const uint4*>(src + e0);
+                const unsigned xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    // a slot outside the cloud (a wrong plan) fails the query before any gather
+                    const bool in = (int)(e0 + i < Kw);
+                    const bool out = (bool)((int)in & (int)(xs[i] >= (unsigned)n));
+                    bad |= out;
+                    slot[4 * q4 + i] = cl.off + ((int)in & (int)!out ? (int)xs[i] : 0);
+                }
+            }
+            bool ok = final_exact(lists + g * kStride, slot, bad, P4, T.perm, qg.x, qg.y, qg.z, cl.off, g, l, nbg,
+                                  min(nbg, max(kk, kn) + 1));
+            __builtin_amdgcn_wave_barrier();
+            // the certificate: the farthest of the taken points is strictly nearer than every
+            // point outside them can be (group-uniform: every lane reads rank Kw - 1)
+            const p3 f = ld3(P4, (int)(ok ? lists[g * kStride + Kw - 1] : (unsigned)wq));
+            const double kb = l2_3(qg.x, qg.y, qg.z, f.x, f.y, f.z);
+            ok = (bool)((int)ok & (int)(kb < take_bound(sr.rho2, lb, s_norm)));
+            const unsigned long long failed = __ballot((int)!ok & (int)(l == 0));
+            if (failed != 0ull) {  // the whole wave is redone: it writes and counts nothing here
+                if (lane == 0) tk.mask[wv] = 1;
+                // (counted as failed: a stored list that did not pass, not a list the source never stored)
+                n_tkf = (unsigned)__popcll(failed & ~__ballot(absent));
+                mode = 0;
+                n_q = 0;
+            } else {
+                n_cand += (unsigned)nbg;
+                n_tkq = kQ;
+                n_sdq = kQ;
+            }
+        }
+    }
+    if (!TK && mode == 1 && !fb_wave) {
         __builtin_amdgcn_wave_barrier();
         int fmode = 0;
         {
@@ -983,6 +1066,36 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
             if ((int)(so >= 0) & (int)mine & (int)(l == 0)) {
                 const p3 f = ld3(P4, (int)rl[Kw - 1]);
                 seedbuf[so + T.perm[wq]] = (float)l2_3(qg.x, qg.y, qg.z, f.x, f.y, f.z);
+            }
+            // for the classes that take: the Kw local tree slots in rank order and Lb, a lower
+            // bound of the exact squared distance of every point that is not among them -- the
+            // list's own rank Kw (the list is sorted by f32 key) and what its bound left out
+            bool stores = false;
+            if (tk.flag != nullptr) stores = (bool)((int)(so >= 0) & (int)((tk.flag[c] & 1) != 0));
+            if ((int)stores & (int)mine) {
+                const size_t at = (size_t)so + (size_t)(wq - cl.off);
+                unsigned k[16];
+                load_head<16>(rl, Kw, l, k);
+                unsigned* dst = tk.lists + at * (size_t)tk.stride;
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const int e0 = l * 16 + 4 * q4;
+                    const unsigned o = (unsigned)cl.off;
+                    if (e0 < Kw)
+                        *reinterpret_cast<uint4*>(dst + e0) =
+                            make_uint4(k[4 * q4] - o, k[4 * q4 + 1] - o, k[4 * q4 + 2] - o, k[4 * q4 + 3] - o);
+                }
+                if (l == 0) {
+                    unsigned tq = Tq[0];
+#pragma unroll
+                    for (int j = 1; j < kQ; ++j) tq = g == j ? Tq[j] : tq;
+                    float lb = narrow_bound(tq, s_norm);
+                    if (nbg > Kw) {
+                        const p3 f = ld3(P4, (int)rl[Kw]);
+                        lb = fminf(lb, key_floor((float)l2_3(qg.x, qg.y, qg.z, f.x, f.y, f.z)));
+                    }
+                    seedbuf[(size_t)tk.lb_off + at] = lb;
+                }
             }
         }
     }
@@ -1074,6 +1187,8 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
             if (n_sdq) atomicAdd(ctr + kSeedStatCol, (unsigned long long)n_sdq);
             if (n_sda) atomicAdd(ctr + kSeedStatCol + 1, (unsigned long long)n_sda);
             if (n_sdf) atomicAdd(ctr + kSeedStatCol + 2, (unsigned long long)n_sdf);
+            if (n_tkq) atomicAdd(ctr + kTakeStatCol, (unsigned long long)n_tkq);
+            if (n_tkr | n_tkf) atomicAdd(ctr + kTakeStatCol + 1, (unsigned long long)n_tkr | ((unsigned long long)n_tkf << 32));
         }
     }
 
@@ -1212,18 +1327,23 @@ __global__ __launch_bounds__(64 * kW) __attribute__((amdgpu_waves_per_eu(kCap <=
 }  // namespace
 
 void launch_lrf8(const View& v, const int32_t* wave_base, int w_lo, int w_hi, int32_t* fb_list, int32_t* fb_count,
-                 hipStream_t s, const SeedRef* seed, float* seedbuf, bool seeded, int seed_mode) {
+                 hipStream_t s, const SeedRef* seed, float* seedbuf, bool seeded, int seed_mode, const TakeArgs* take,
+                 bool taking) {
     const int nb = (w_hi - w_lo + kW - 1) / kW;
     if (nb <= 0) return;
-    if (seeded)
+    const TakeArgs tk = take ? *take : TakeArgs{nullptr, nullptr, nullptr, 0, 0, 0};
+    if (taking)
+        hipLaunchKernelGGL((k_lrf8<true, false, true>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds,
+                           v.t3.lo, v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode, tk);
+    else if (seeded)
         hipLaunchKernelGGL((k_lrf8<true, false>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
-                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode, tk);
     else if (seed != nullptr)
         hipLaunchKernelGGL((k_lrf8<false, true>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
-                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode, tk);
     else
         hipLaunchKernelGGL((k_lrf8<false, false>), dim3(nb), dim3(64 * kW), 0, s, v, v.cloud_of, v.setup, v.clouds, v.t3.lo,
-                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode);
+                           v.t3.hi, v.t3.tpt64, wave_base, w_lo, w_hi, fb_list, fb_count, seed, seedbuf, seed_mode, tk);
 }
 
 }  // namespace se3icp

@@ -150,9 +150,26 @@ void launch_lrf_list(const View& v, const int32_t* qlist, const int32_t* qcount,
 // storing and unseeded clouds (seeded = 0; seed may be null) or of seeded clouds only.
 // seed_mode: se3icp_set_lrf_seeding's 0, 2 (seeds halved) or 3 (seeds times 4).
 struct SeedRef { int32_t store; int32_t load; double rho2; };
+// Taking (graph.hpp, graph_plan_takes): a seeded cloud whose selecting slot has its source's tree
+// order takes the source's neighbour lists instead of searching.  flag[c] & 1: cloud c's waves
+// store, beside their seeds, every kept query's Kw local tree slots in rank order (lists, `stride`
+// entries per query, at seed offset + local tree position) and the bound Lb of what lies outside
+// them (seedbuf[lb_off + the same index]); flag[c] & 2: cloud c takes.  taking = true launches the
+// taking clouds' waves, which set their byte of `mask` (zeroed by the caller) where they could not
+// take; a seeded launch over the same wave table with the mask runs those waves only.  mode:
+// se3icp_set_lrf_taking's 0 or 2 (every Lb halved).  Null flag / mask: nothing stores / every
+// wave runs.
+struct TakeArgs {
+    const int32_t* flag;
+    uint32_t* lists;
+    unsigned char* mask;
+    int32_t stride;
+    int32_t lb_off;
+    int32_t mode;
+};
 void launch_lrf8(const View& v, const int32_t* wave_base, int w_lo, int w_hi, int32_t* fb_list, int32_t* fb_count,
                  hipStream_t s, const SeedRef* seed = nullptr, float* seedbuf = nullptr, bool seeded = false,
-                 int seed_mode = 0);
+                 int seed_mode = 0, const TakeArgs* take = nullptr, bool taking = false);
 // neighbourhoods over kSmallK (k_knn_big.hip): one wavefront per query with a global-memory
 // candidate buffer of `cap` entries per block; queries with Kw = min(k, n) <= k_min are
 // skipped (the LDS kernels'); qlist = nullptr: every point

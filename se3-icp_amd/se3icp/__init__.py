@@ -18,7 +18,7 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            expand_edges, last_graph_stats, register_graph, register_graph_device,
                            register_graph_report, register_graph_traced, register_sequence, sequence_edges,
                            set_batch_sharing, set_lrf_seeding, last_seed_stats,
-                           set_tree_sharing, last_tree_stats,
+                           set_tree_sharing, last_tree_stats, set_lrf_taking, last_take_stats,
                            voxel_downsample, voxel_downsample_device,
                            edge_inits, last_init_stats, set_pose_seeding, transform_device, transform_points)
 from ._lib import Report, ReportOptions  # noqa: F401
@@ -33,6 +33,7 @@ __all__ = [
     "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
     "register_graph_report", "register_graph_traced", "last_graph_stats",
     "set_batch_sharing", "set_lrf_seeding", "last_seed_stats", "set_tree_sharing", "last_tree_stats",
+    "set_lrf_taking", "last_take_stats",
     "voxel_downsample", "voxel_downsample_device",
     "edge_inits", "transform_points", "transform_device", "set_pose_seeding", "last_init_stats",
 ]

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_register_graph", "se3icp_register_graph_device", "se3icp_register_graph_report",
     "se3icp_register_graph_report_device", "se3icp_last_graph_stats", "se3icp_set_batch_sharing",
     "se3icp_set_lrf_seeding", "se3icp_last_seed_stats", "se3icp_set_tree_sharing", "se3icp_last_tree_stats",
+    "se3icp_set_lrf_taking", "se3icp_last_take_stats",
     "se3icp_report_version", "se3icp_register_batch_report", "se3icp_register_batch_report_device",
     "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
     "se3icp_request_report", "se3icp_get_report",
@@ -141,6 +142,8 @@ GRAPH_STATS = ["clouds", "uses", "classes", "classes_full", "adopted", "rejected
                "bytes_uploaded"]
 # se3icp_last_seed_stats
 SEED_STATS = ["classes_seeded", "queries_seeded", "queries_unseeded", "queries_failed"]
+# se3icp_last_take_stats
+TAKE_STATS = ["classes_taking", "queries_taken", "queries_redone", "queries_failed"]
 # se3icp_last_init_stats
 INIT_STATS = ["posed_edges", "posed_variants", "classes_seeded_across"]
 # se3icp_last_tree_stats
@@ -254,8 +257,9 @@ def load():
     L.se3icp_set_lrf_exact.argtypes = [C.c_int, C.c_int]
     L.se3icp_set_nn_events.argtypes = [C.c_int, C.c_int]
     # (se3icp_set_batch_sharing(int, int), se3icp_set_lrf_seeding(int, int),
-    # se3icp_last_seed_stats(int, int64_t*, int), se3icp_set_tree_sharing(int, int) and
-    # se3icp_last_tree_stats(int, int64_t*, int) are called with ctypes' default conversions and
+    # se3icp_last_seed_stats(int, int64_t*, int), se3icp_set_tree_sharing(int, int),
+    # se3icp_last_tree_stats(int, int64_t*, int), se3icp_set_lrf_taking(int, int) and
+    # se3icp_last_take_stats(int, int64_t*, int) are called with ctypes' default conversions and
     # resolved at their first call: SE3ICP_LIB may name an older build for an A/B run)
     _lib = L
     return L

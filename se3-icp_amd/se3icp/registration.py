@@ -968,6 +968,22 @@ def last_seed_stats(device: int = 0) -> dict:
     return {k: int(out[i]) for i, k in enumerate(_lib.SEED_STATS)}
 
 
+def set_lrf_taking(mode: int, device: int = 0) -> None:
+    """Whether a seeded class that has its source's kd-tree order takes the source's neighbour
+    lists, re-checked under its own scale, instead of searching, on the engine behind `device`
+    (se3icp_set_lrf_taking): 0 take (the default), 1 off, 2 a diagnostic (every stored bound
+    halved: every wavefront is redone as a seeded one).  Results are bitwise the same in every
+    mode; last_take_stats() describes the last call."""
+    _lib.check(_lib.load().se3icp_set_lrf_taking(int(device), int(mode)), "set_lrf_taking")
+
+
+def last_take_stats(device: int = 0) -> dict:
+    """Taking counters of the last registration call on `device` (se3icp_last_take_stats)."""
+    out = (C.c_int64 * len(_lib.TAKE_STATS))()
+    _lib.check(_lib.load().se3icp_last_take_stats(int(device), out, len(_lib.TAKE_STATS)), "last_take_stats")
+    return {k: int(out[i]) for i, k in enumerate(_lib.TAKE_STATS)}
+
+
 def set_tree_sharing(mode: int, device: int = 0) -> None:
     """Whether the later slots of a confirmed cloud take its first slot's kd-tree order on the
     engine behind `device` (se3icp_set_tree_sharing): 0 adopt (the default), 1 off, every slot

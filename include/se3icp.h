@@ -649,6 +649,57 @@ typedef struct se3icp_trace {
 } se3icp_trace;
 int se3icp_set_trace(int device, se3icp_trace* trace);
 
+/* The setup's per-point arrays of ONE pair of the next registration call on `device`
+ * (diagnostic, of the kind of se3icp_trace; the tests hold them to long-double references and
+ * compare them bitwise between the entries and the sharing modes).  What is recorded is what
+ * the loop is about to consume: the arrays of cloud slots 2 * pair (source) and 2 * pair + 1
+ * (target) as they stand when the setup is complete and before the first iteration is queued,
+ * whichever entry, sharing mode or kernel produced them.
+ *   xyz      [n * 3] AoS, in the loop's frame: normalized ((p + (-norm_center)) * norm_scale)
+ *            for the run_se3_* methods, the input for run_icp;
+ *   rows     [n * 12] the weighted SE(3) element of every point,
+ *            (alpha R00 R10 R20 R01 R11 R21 R02 R12 R22, beta t0 t1 t2): the columns of the
+ *            TOLDI frame, then its translation.  Only for methods with frames (run_se3_*);
+ *   normals  [n * 3] AoS; only where the method estimates normals for that side;
+ *   conf     [n] lounge confidences; only for se3_gicp_with_cf.
+ * `written` says which arrays were filled (SE3ICP_SETUP_* bits): an array the method does not
+ * produce, or that is NULL, is left alone.  The scalars are the cloud's device-side setup
+ * record.  Any array may be NULL; `cap` is the number of points the side's arrays have room
+ * for: a cloud with more fails the call with SE3ICP_ERR_INVALID_ARG before its loop.
+ * Armed by se3icp_set_setup_record as a trace is: one-shot, for the next registration call on
+ * that engine (device | slot << 8); the pointers are kept until that call returns; NULL
+ * disarms; a pair outside the call's results is SE3ICP_ERR_INVALID_ARG from that call.  After a
+ * sweep `pair` indexes the result array (v * n_pairs + p) and the record shows variant v's
+ * rows; after a graph call it is the edge index (a posed edge's source is the posed cloud).
+ * Armed, the call waits once more for the device; unarmed, a call queues exactly what it
+ * queues without this entry.  Never used by bench.py. */
+#define SE3ICP_SETUP_XYZ 1
+#define SE3ICP_SETUP_ROWS 2
+#define SE3ICP_SETUP_NORMALS 4
+#define SE3ICP_SETUP_CONF 8
+typedef struct se3icp_setup_side {
+    double* xyz;            /* [cap * 3] */
+    double* rows;           /* [cap * 12] */
+    double* normals;        /* [cap * 3] */
+    double* conf;           /* [cap] */
+    int64_t cap;            /* points the arrays have room for */
+    int64_t n;              /* out: points of the cloud */
+    double norm_center[3];  /* out: the cloud's setup scalars */
+    double norm_scale;
+    double f32_center[3];
+    double alpha;
+    double beta;
+    int32_t written;        /* out: SE3ICP_SETUP_* bits of the arrays filled */
+    int32_t _reserved;
+} se3icp_setup_side;
+typedef struct se3icp_setup_record {
+    int32_t pair;           /* result index within the next call */
+    int32_t recorded;       /* out: 1 once the record was taken */
+    se3icp_setup_side src, tgt;
+} se3icp_setup_record;
+int se3icp_setup_record_version(void);  /* 1 */
+int se3icp_set_setup_record(int device, se3icp_setup_record* rec);
+
 /* Diagnostic: which kernels compute the setup's kNN / TOLDI / normals on `device`:
  *   0 = the default: eight queries per wavefront (k_lrf8), the exact one-query-per-wavefront
  *       kernel for the queries it hands over, the global-buffer kernel for k > 128;

@@ -743,6 +743,17 @@ int se3icp_set_trace(int device, se3icp_trace* trace) {
     return 0;
 }
 
+int se3icp_setup_record_version(void) { return 1; }
+
+int se3icp_set_setup_record(int device, se3icp_setup_record* rec) {
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    if (rec && (rec->pair < 0 || rec->src.cap < 0 || rec->tgt.cap < 0)) return SE3ICP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_setup_record(rec);
+    return 0;
+}
+
 int se3icp_set_lrf_exact(int device, int exact_only) {
     Engine* e = usable_engine(device);
     if (!e) return SE3ICP_ERR_NO_DEVICE;

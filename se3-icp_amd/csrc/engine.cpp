@@ -668,11 +668,21 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
     se3icp_trace* tr = c->tr = trace_;  // one-shot: the record covers this call only
     trace_ = nullptr;
+    se3icp_setup_record* sr = c->sr = setup_rec_;  // one-shot likewise
+    setup_rec_ = nullptr;
     pose_raw_.clear();  // (a call without a posed edge plans its seeds over clouds)
     pose_rigid_.clear();
     if (args) return args;
     if (tr && (tr->pair < 0 || (int64_t)tr->pair >= nslots || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
     if (tr) tr->iters_recorded = 0;
+    if (sr && (sr->pair < 0 || (int64_t)sr->pair >= nslots || sr->src.cap < 0 || sr->tgt.cap < 0))
+        return SE3ICP_ERR_INVALID_ARG;
+    if (sr) {
+        c->sr_pair = sr->pair;
+        sr->recorded = 0;
+        sr->src.n = sr->tgt.n = 0;
+        sr->src.written = sr->tgt.written = 0;
+    }
     if (rest) return rest;
     HIPCHK(hipSetDevice(dev_));
     c->s = user_stream ? user_stream : stream_;
@@ -708,6 +718,17 @@ int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const
     HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
     for (double& t : trace_prev_) t = 0;
     HIPCHK(hipEventRecord(ev_[13], s));
+    // The armed setup record, taken here: every entry's setup is complete (the kNN / frame /
+    // normal kernels, k_graph_share's copies, k_sweep_expand's weighted rows) and nothing of the
+    // loop is queued.  What ran between the end of the setup and this point -- the 12-D trees,
+    // prepare_pairs, setup_chunks, the two clears above -- reads xyz64 / fr64 and writes the
+    // trees' own buffers, the work tables, cert, gcost, cls, corr_idx and stats: none of them
+    // writes xyz64, fr64, nrm64, conf64 or the setup table, and the loop only reads them, so
+    // these are the arrays the loop consumes.  Unarmed, nothing is queued here.
+    if (c.sr) {
+        rc = record_setup(c.sr, c.sr_pair, s);
+        if (rc) return rc;
+    }
     const ReportReq rq{ropts, reports};
     return run_loop(npairs, ns, mp.kind, mp.est, vprm, pairs_per_variant, sweep, c.tr, out, s,
                     (ropts && reports) ? &rq : nullptr);
@@ -1552,7 +1573,13 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
             gtr.pair = tr->pair - v0 * P;
             use = &gtr;
         }
-        rc = run_pairs(mp, g * P, vns.data(), vnt.data(), variants + v0, P, true, Call{use, s}, out + (size_t)v0 * P,
+        // the armed setup record likewise: the group's replica of the pair, after its expansion
+        Call gcall{use, s};
+        if (call.sr && call.sr_pair >= v0 * P && call.sr_pair < (v0 + g) * P) {
+            gcall.sr = call.sr;
+            gcall.sr_pair = call.sr_pair - v0 * P;
+        }
+        rc = run_pairs(mp, g * P, vns.data(), vnt.data(), variants + v0, P, true, gcall, out + (size_t)v0 * P,
                        ropts, reports ? reports + (size_t)v0 * P : nullptr);
         if (use) tr->iters_recorded = gtr.iters_recorded;
         if (rc && rc != SE3ICP_ERR_NONFINITE) return rc;
@@ -1869,6 +1896,68 @@ int Engine::record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t
         tr->iters_recorded = it;
     }
     phase_of_it = S.done ? PHASE_IDLE : S.phase;
+    return 0;
+}
+
+// The armed setup record of pair `pair` (cloud slots 2 * pair, 2 * pair + 1 of the layout
+// run_pairs was given): the device's setup table first, which says what the setup produced for
+// each side, then the arrays.  Called with the setup queued and no loop work behind it.
+int Engine::record_setup(se3icp_setup_record* rec, int pair, hipStream_t s) {
+    if (pair < 0 || 2 * pair + 1 >= nclouds_) return SE3ICP_ERR_INVALID_ARG;
+    CloudSetup st[2];
+    HIPCHK(hipMemcpyAsync(st, (const CloudSetup*)d_setup_.p + 2 * pair, sizeof(st), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t ld = (size_t)ld_;
+    std::vector<double> col;
+    for (int side = 0; side < 2; ++side) {
+        se3icp_setup_side& o = side == 0 ? rec->src : rec->tgt;
+        const CloudDev& cd = h_clouds_[2 * pair + side];
+        const CloudSetup& cs = st[side];
+        const size_t n = (size_t)cd.n, off = (size_t)cd.off;
+        o.n = cd.n;
+        if ((int64_t)cd.n > o.cap && (o.xyz || o.rows || o.normals || o.conf)) return SE3ICP_ERR_INVALID_ARG;
+        for (int a = 0; a < 3; ++a) {
+            o.norm_center[a] = cs.norm_center[a];
+            o.f32_center[a] = cs.f32_center[a];
+        }
+        o.norm_scale = cs.norm_scale;
+        o.alpha = cs.alpha;
+        o.beta = cs.beta;
+        // the SoA columns [3][ld] of the points and the normals into AoS
+        auto columns = [&](const DevBuf& b, double* out) -> int {
+            col.resize(3 * n);
+            for (int a = 0; a < 3; ++a)
+                HIPCHK(hipMemcpyAsync(col.data() + a * n, (const double*)b.p + a * ld + off, sizeof(double) * n,
+                                      hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < n; ++i)
+                for (int a = 0; a < 3; ++a) out[3 * i + a] = col[a * n + i];
+            return 0;
+        };
+        int32_t written = 0;
+        if (o.xyz) {
+            const int rc = columns(d_xyz64_, o.xyz);
+            if (rc) return rc;
+            written |= SE3ICP_SETUP_XYZ;
+        }
+        if (o.rows && cs.k_lrf > 0) {
+            HIPCHK(hipMemcpyAsync(o.rows, (const double*)d_fr64_.p + 12 * off, sizeof(double) * 12 * n,
+                                  hipMemcpyDeviceToHost, s));
+            written |= SE3ICP_SETUP_ROWS;
+        }
+        if (o.normals && cs.k_nrm > 0) {
+            const int rc = columns(d_nrm64_, o.normals);
+            if (rc) return rc;
+            written |= SE3ICP_SETUP_NORMALS;
+        }
+        if (o.conf && cs.want_conf) {
+            HIPCHK(hipMemcpyAsync(o.conf, (const double*)d_conf64_.p + off, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+            written |= SE3ICP_SETUP_CONF;
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        o.written = written;
+    }
+    rec->recorded = 1;
     return 0;
 }
 

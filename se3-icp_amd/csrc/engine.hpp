@@ -90,6 +90,7 @@ class Engine {
     std::mutex& mutex() { return mu_; }
     void set_profiling(bool on) { profile_ = on; }
     void set_trace(se3icp_trace* t) { trace_ = t; }
+    void set_setup_record(se3icp_setup_record* r) { setup_rec_ = r; }
     void set_lrf_exact(int mode) { lrf_exact_only_ = mode; }
     void set_nn_events(bool on) { nn_events_ = on; }
     void set_batch_sharing(int level) { batch_sharing_ = level; }
@@ -196,9 +197,14 @@ class Engine {
     // stream, the kernel times' reset and the begin event.  The entry's own argument checks
     // surround the trace's: `args` is the status of those before it, `rest` (evaluated by the
     // entry only when `args` is 0) of those after it.
+    // The armed setup record (se3icp_set_setup_record) rides beside the trace: taken and validated
+    // with it, sr_pair the recorded pair's index among the pairs run_pairs is given (a sweep
+    // remaps it per group as it does the trace's).
     struct Call {
         se3icp_trace* tr = nullptr;
         hipStream_t s = nullptr;
+        se3icp_setup_record* sr = nullptr;
+        int sr_pair = -1;
     };
     int open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c);
     // The clouds back to back in the SoA columns: offsets, chunk list, inputs (uploaded, or
@@ -288,6 +294,8 @@ class Engine {
     int tree_sharing_ = 0;
     se3icp_trace* trace_ = nullptr;      // armed per-iteration record of one pair (se3icp_set_trace)
     int record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t s);
+    se3icp_setup_record* setup_rec_ = nullptr;  // armed setup record of one pair (se3icp_set_setup_record)
+    int record_setup(se3icp_setup_record* rec, int pair, hipStream_t s);
     double trace_prev_[kStatCols] = {};
     std::vector<CloudDev> h_clouds_;
     std::vector<CloudSetup> h_setup_;

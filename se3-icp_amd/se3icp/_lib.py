@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_set_initial_transform", "se3icp_set_pose_seeding", "se3icp_last_init_stats",
     "se3icp_transform_points", "se3icp_transform_device",
     "se3icp_set_profiling", "se3icp_last_kernel_times", "se3icp_last_kernel_times_n", "se3icp_set_trace", "se3icp_set_lrf_exact",
-    "se3icp_set_nn_events",
+    "se3icp_set_nn_events", "se3icp_setup_record_version", "se3icp_set_setup_record",
     # include/se3icp_cc.h: metrics and pose files of the benchmark drivers (host only)
     "se3icp_cc_rot_3d", "se3icp_cc_angular_error_so3", "se3icp_cc_angular_error_so3_alt",
     "se3icp_cc_error_filterreg", "se3icp_cc_rot2euler", "se3icp_cc_avg_eul_error",
@@ -134,6 +134,38 @@ class Trace(C.Structure):
         ("phase", C.POINTER(C.c_int32)),
         ("iters_recorded", C.c_int32),
         ("_reserved", C.c_int32),
+    ]
+
+
+SETUP_XYZ, SETUP_ROWS, SETUP_NORMALS, SETUP_CONF = 1, 2, 4, 8
+
+
+class SetupSide(C.Structure):
+    """se3icp_setup_side."""
+    _fields_ = [
+        ("xyz", C.POINTER(C.c_double)),
+        ("rows", C.POINTER(C.c_double)),
+        ("normals", C.POINTER(C.c_double)),
+        ("conf", C.POINTER(C.c_double)),
+        ("cap", C.c_int64),
+        ("n", C.c_int64),
+        ("norm_center", C.c_double * 3),
+        ("norm_scale", C.c_double),
+        ("f32_center", C.c_double * 3),
+        ("alpha", C.c_double),
+        ("beta", C.c_double),
+        ("written", C.c_int32),
+        ("_reserved", C.c_int32),
+    ]
+
+
+class SetupRecord(C.Structure):
+    """se3icp_setup_record."""
+    _fields_ = [
+        ("pair", C.c_int32),
+        ("recorded", C.c_int32),
+        ("src", SetupSide),
+        ("tgt", SetupSide),
     ]
 
 
@@ -254,6 +286,9 @@ def load():
     L.se3icp_last_kernel_times.argtypes = [C.c_int, dp]
     L.se3icp_last_kernel_times_n.argtypes = [C.c_int, dp, C.c_int]
     L.se3icp_set_trace.argtypes = [C.c_int, C.POINTER(Trace)]
+    if hasattr(L, "se3icp_setup_record_version"):  # (SE3ICP_LIB may name an older build for an A/B run)
+        L.se3icp_setup_record_version.restype = C.c_int
+        L.se3icp_set_setup_record.argtypes = [C.c_int, C.POINTER(SetupRecord)]
     L.se3icp_set_lrf_exact.argtypes = [C.c_int, C.c_int]
     L.se3icp_set_nn_events.argtypes = [C.c_int, C.c_int]
     # (se3icp_set_batch_sharing(int, int), se3icp_set_lrf_seeding(int, int),

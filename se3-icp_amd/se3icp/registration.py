@@ -467,6 +467,43 @@ def _armed_trace(device: int, slot: int, n_src: int, max_iters: int):
     trace.update({k: v[:n] for k, v in tr.items()})
 
 
+@contextlib.contextmanager
+def setup_record(pair: int, n_src: int, n_tgt: int, device: int = 0):
+    """Arm the setup record (se3icp_set_setup_record) of result slot `pair` -- a source of n_src
+    and a target of n_tgt points -- for the one registration call made inside the block, through
+    any register_* entry (host, device, stream, sweep: slot v * n_pairs + p, graph: the edge).
+    The dict it yields holds, after the block, per side "src" / "tgt" a dict of
+    xyz (n, 3), rows (n, 12), normals (n, 3), conf (n,) -- None where the method does not produce
+    the array -- and the setup scalars norm_center, norm_scale, f32_center, alpha, beta, n."""
+    L = _lib.load()
+    rec = _lib.SetupRecord()
+    rec.pair = int(pair)
+    bufs = {}
+    for name, n in (("src", int(n_src)), ("tgt", int(n_tgt))):
+        side = getattr(rec, name)
+        bufs[name] = {"xyz": np.zeros((n, 3)), "rows": np.zeros((n, 12)), "normals": np.zeros((n, 3)),
+                      "conf": np.zeros(n)}
+        for key, a in bufs[name].items():
+            setattr(side, key, a.ctypes.data_as(_DP))
+        side.cap = n
+    _lib.check(L.se3icp_set_setup_record(device, C.byref(rec)), "set_setup_record")
+    out = {}
+    try:
+        yield out
+    finally:
+        L.se3icp_set_setup_record(device, None)
+    if not rec.recorded:
+        raise _lib.Se3IcpError(_lib.ERR_INTERNAL, "the call inside the block took no setup record")
+    bits = {"xyz": _lib.SETUP_XYZ, "rows": _lib.SETUP_ROWS, "normals": _lib.SETUP_NORMALS, "conf": _lib.SETUP_CONF}
+    for name in ("src", "tgt"):
+        side = getattr(rec, name)
+        n = int(side.n)
+        d = {key: (bufs[name][key][:n] if side.written & bit else None) for key, bit in bits.items()}
+        d.update(n=n, norm_center=np.array(side.norm_center[:]), norm_scale=float(side.norm_scale),
+                 f32_center=np.array(side.f32_center[:]), alpha=float(side.alpha), beta=float(side.beta))
+        out[name] = d
+
+
 def register_batch_traced(pairs, method: str, params: _lib.Params | None = None, pair: int = 0,
                           max_iters: int = 160, device: int = 0):
     """register_batch with the per-iteration record of one pair (se3icp_set_trace): the

@@ -4,6 +4,7 @@ the reference's interface.  No compute is launched here."""
 import ctypes as C
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -132,3 +133,43 @@ def test_kitti_scans_do_not_depend_on_the_casting_threads():
     got, _ = datasets.kitti_like_sequence(9, seed=4, scan_indices=range(8), workers=8)
     for k in range(8):
         np.testing.assert_array_equal(got[k], ref[k])
+
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def test_setup_record_layout_matches_the_ctypes_mirror(tmp_path):
+    from se3icp import _lib
+    cc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    if not cc:
+        pytest.skip("hipcc not available")
+    side = [f for f, _ in _lib.SetupSide._fields_]
+    rec = [f for f, _ in _lib.SetupRecord._fields_]
+    src = tmp_path / "layout.cpp"
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "se3icp.h"', "int main() {",
+             '  std::printf("%zu %zu\\n", sizeof(se3icp_setup_side), sizeof(se3icp_setup_record));']
+    lines += [f'  std::printf("%zu %zu\\n", offsetof(se3icp_setup_side, {f}), sizeof(((se3icp_setup_side*)0)->{f}));'
+              for f in side]
+    lines += [f'  std::printf("%zu %zu\\n", offsetof(se3icp_setup_record, {f}), sizeof(((se3icp_setup_record*)0)->{f}));'
+              for f in rec]
+    lines += ["  return 0;", "}"]
+    src.write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([cc, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    out = [tuple(int(x) for x in ln.split()) for ln in subprocess.run([exe], capture_output=True, text=True,
+                                                                      check=True).stdout.splitlines()]
+    assert out[0] == (C.sizeof(_lib.SetupSide), C.sizeof(_lib.SetupRecord))
+    want = [(getattr(_lib.SetupSide, f).offset, getattr(_lib.SetupSide, f).size) for f in side]
+    want += [(getattr(_lib.SetupRecord, f).offset, getattr(_lib.SetupRecord, f).size) for f in rec]
+    assert out[1:] == want
+    assert (_lib.SETUP_XYZ, _lib.SETUP_ROWS, _lib.SETUP_NORMALS, _lib.SETUP_CONF) == (1, 2, 4, 8)
+
+
+def test_setup_record_arguments_without_a_device():
+    """The version entry, and arming either fails loudly without a device or accepts NULL."""
+    import se3icp
+    from se3icp import _lib
+    lib = se3icp.load()
+    assert lib.se3icp_setup_record_version() == 1
+    rc = lib.se3icp_set_setup_record(0, None)
+    assert rc == (_lib.OK if se3icp.device_count() > 0 else _lib.ERR_NO_DEVICE)

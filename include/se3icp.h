@@ -511,6 +511,31 @@ int se3icp_estimate_normals(int device, const double* xyz, int64_t n, int k, dou
 int se3icp_nn(int device, const double* query, int64_t nq, const double* data, int64_t nd, int dim,
               int32_t* idx, double* d2, int32_t* num_rechecked);
 
+/* The loop's correspondence stage over a GIVEN pose sequence (diagnostic): the
+ * setup of se3icp_nn (host-filled vectors, kd-trees, a neutral setup table with `alpha`), then
+ * step k = 1 .. n_steps is iteration k of a one-pair run whose pose is poses[k - 1] (row-major
+ * 4x4, bottom row bitwise (0, 0, 0, 1)): the loop's own k_nn_prep settles what the NN
+ * certificates allow, its search (with the inline f64 recheck) resolves the rest, and matches and
+ * certificates carry over to the next step.  From step restart_at on (0: never) the phase counts
+ * as started at restart_at, which voids every earlier certificate.
+ * dim 3: a query is the point poses[k] * query[i].  dim 12: a query row is [alpha x, alpha y,
+ * alpha z, t] in the packing of the frames ([R00 R10 R20 R01 R11 R21 R02 R12 R22 t0 t1 t2]) with
+ * (x y z) orthonormal, moved as a frame; data rows are plain 12-vectors.  The certificates assume
+ * the orthonormality and `alpha`; the entry does not check either.
+ * Outputs, all in query order and any of them NULL: per step and query [n_steps * nq] the match
+ * `idx`, the stored distance `dist` and the certificate words after the step (cert_iter -1: none;
+ * cert_d1 / cert_l2: the bounds D1 / L2; cert_j: the certified match); per step [n_steps] the
+ * queries k_nn_prep did not settle (`searched`), how many of those went to the
+ * one-query-per-wave list (`single`) and the queries re-resolved in f64 (`rechecked`).
+ * SE3ICP_ERR_INVALID_ARG for a NULL query / data / poses, dim not 3 or 12, n_steps <= 0, a
+ * non-finite alpha or pose entry, a wrong bottom row, restart_at outside [0, n_steps];
+ * SE3ICP_ERR_EMPTY_CLOUD for nq or nd <= 0 -- all before the device is looked up. */
+int se3icp_nn_sequence_version(void);  /* 1 */
+int se3icp_nn_sequence(int device, const double* query, int64_t nq, const double* data, int64_t nd, int dim,
+                       double alpha, int32_t n_steps, const double* poses, int32_t restart_at, int32_t* idx,
+                       float* dist, float* cert_d1, float* cert_l2, int32_t* cert_iter, int32_t* cert_j,
+                       int32_t* searched, int32_t* single, int32_t* rechecked);
+
 /* ------------------------------------------------------------- data generators
  * The synthetic registration problems of examples/benchmark_synthetic.cpp:91-160
  * (add_noise_to_point_cloud B_SYN:13-56, RandomDownSample, T_c applied to the target),

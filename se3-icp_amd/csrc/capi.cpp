@@ -693,6 +693,27 @@ int se3icp_nn(int device, const double* query, int64_t nq, const double* data, i
     return e->nn(query, nq, data, nd, dim, idx, d2, num_rechecked);
 }
 
+// The loop's NN prep and search over a given pose sequence (diagnostic).
+// Arguments are checked before the device is looked up.
+int se3icp_nn_sequence_version(void) { return 1; }
+
+int se3icp_nn_sequence(int device, const double* query, int64_t nq, const double* data, int64_t nd, int dim,
+                       double alpha, int32_t n_steps, const double* poses, int32_t restart_at, int32_t* idx,
+                       float* dist, float* cert_d1, float* cert_l2, int32_t* cert_iter, int32_t* cert_j,
+                       int32_t* searched, int32_t* single, int32_t* rechecked) {
+    if (!query || !data || !poses || (dim != 3 && dim != 12) || n_steps <= 0 || !std::isfinite(alpha))
+        return SE3ICP_ERR_INVALID_ARG;
+    if (restart_at < 0 || restart_at > n_steps) return SE3ICP_ERR_INVALID_ARG;
+    for (int32_t k = 0; k < n_steps; ++k)
+        if (!se3icp::pose_is_valid(poses + 16 * (size_t)k)) return SE3ICP_ERR_INVALID_ARG;
+    if (nq <= 0 || nd <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    const Engine::NNSequenceOut out{idx, dist, cert_d1, cert_l2, cert_iter, cert_j, searched, single, rechecked};
+    return e->nn_sequence(query, nq, data, nd, dim, alpha, n_steps, poses, restart_at, out);
+}
+
 // ------------------------------------------------------------------ voxel-grid downsample
 // Arguments are checked before the device is looked up, as the sweeps' are (voxel.hpp).
 int se3icp_voxel_version(void) { return 1; }

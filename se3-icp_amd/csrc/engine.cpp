@@ -2041,14 +2041,11 @@ int Engine::estimate_normals(const double* xyz, int64_t n, int k, double* normal
     return 0;
 }
 
-// Exact 1-NN of arbitrary query vectors among data vectors (3 or 12 dims): the vectors
-// are placed in the source/target slots of a one-pair batch with the identity pose, the
-// kd-trees are built over them, and the loop's NN kernels (with their inline f64 recheck) run once.
-int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, int dim, int32_t* idx, double* d2,
-               int32_t* num_rechecked) {
-    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    if (!query || !data || !idx || (dim != 3 && dim != 12)) return SE3ICP_ERR_INVALID_ARG;
-    if (nq <= 0 || nd <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+// The setup of the NN stage entries (nn, nn_sequence): the vectors in the source / target slots
+// of a one-pair batch, host-filled SoA, the kd-trees, the chunks, a neutral setup table with
+// `alpha`, and the pair record of iteration 1 with the identity pose -- everything up to the
+// launches.  The arguments are valid.
+int Engine::nn_setup(const double* query, int64_t nq, const double* data, int64_t nd, int dim, double alpha) {
     HIPCHK(hipSetDevice(dev_));
     hipStream_t s = stream_;
     npairs_ = 1;
@@ -2060,10 +2057,10 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
         !ensure<int32_t>(d_rechecked_, 1))
         return SE3ICP_ERR_OUT_OF_MEMORY;
     // k_nn_prep reads the source cloud's alpha for every position: a neutral table of this
-    // call's own (an engine whose first call this is has none; alpha only weighs certificates
-    // of earlier searches, and a one-search run has none)
+    // call's own (an engine whose first call this is has none)
     h_setup_.assign(2, CloudSetup{});
     for (CloudSetup& st : h_setup_) st.alpha = st.beta = st.norm_scale = 1.0;
+    h_setup_[0].alpha = alpha;
     h_setup_[1].is_target = 1;
     HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * 2, hipMemcpyHostToDevice, s));
     h_clouds_.assign(2, CloudDev{});
@@ -2074,7 +2071,9 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
     tree_L_ = tree_depth_for((int)std::max(nq, nd));
     // SoA f64 masters + f32 copies, filled on the host (diagnostic entry point)
     const size_t L = ld_;
-    std::vector<int32_t> cof(L, 0);
+    // (members: the copies below are asynchronous and outlive this function)
+    std::vector<int32_t>& cof = nn_cof_;
+    cof.assign(L, 0);
     for (int64_t i = nq; i < ntot; ++i) cof[i] = 1;
     double cen[3] = {0, 0, 0};
     if (dim == 3) {
@@ -2082,8 +2081,10 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
             for (int a = 0; a < 3; ++a) cen[a] += data[3 * j + a];
         for (int a = 0; a < 3; ++a) cen[a] /= (double)nd;
     }
-    std::vector<double> m64((size_t)dim * L, 0.0);
-    std::vector<float> m32((size_t)dim * L, 0.f);
+    std::vector<double>& m64 = nn_m64_;
+    std::vector<float>& m32 = nn_m32_;
+    m64.assign((size_t)dim * L, 0.0);
+    m32.assign((size_t)dim * L, 0.f);
     double nb = 0;
     for (int64_t i = 0; i < ntot; ++i) {
         const double* row = i < nq ? query + dim * i : data + dim * (i - nq);
@@ -2107,7 +2108,7 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
     if (rc) return rc;
     rc = setup_chunks(1, s);
     if (rc) return rc;
-    PairDev P;
+    PairDev& P = nn_pair_;
     std::memset(&P, 0, sizeof(P));
     P.T[0] = P.T[5] = P.T[10] = 1.0;
     P.src = 0;
@@ -2122,6 +2123,21 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
     HIPCHK(hipMemsetAsync(d_flag_count_.p, 0, 3 * sizeof(int32_t), s));
     HIPCHK(hipMemsetAsync(d_rechecked_.p, 0, sizeof(int32_t), s));
     HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * L, s));
+    return 0;
+}
+
+// Exact 1-NN of arbitrary query vectors among data vectors (3 or 12 dims): the vectors
+// are placed in the source/target slots of a one-pair batch with the identity pose, the
+// kd-trees are built over them, and the loop's NN kernels (with their inline f64 recheck) run once.
+int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, int dim, int32_t* idx, double* d2,
+               int32_t* num_rechecked) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    if (!query || !data || !idx || (dim != 3 && dim != 12)) return SE3ICP_ERR_INVALID_ARG;
+    if (nq <= 0 || nd <= 0) return SE3ICP_ERR_EMPTY_CLOUD;
+    // (alpha only weighs certificates of earlier searches, and a one-search run has none)
+    int rc = nn_setup(query, nq, data, nd, dim, 1.0);
+    if (rc) return rc;
+    hipStream_t s = stream_;
     View v = view();
     launch_nn_prep(v, nullptr, s);
     launch_nn(v, dim, s);
@@ -2151,6 +2167,75 @@ int Engine::nn(const double* query, int64_t nq, const double* data, int64_t nd, 
             }
             d2[i] = r;
         }
+    }
+    return 0;
+}
+
+// The loop's k_nn_prep and search of a one-pair run whose poses are given: step k is
+// iteration k.  Before it the host writes, stream-ordered, what pair_open_iteration and
+// k_reduce_final leave for an iteration's k_nn_prep -- the pair record (pose, iteration, phase
+// start), the pose's ring row, and the cleared single-query counts and cost-class counts --
+// and launches the loop's own two kernels; corr_idx and the certificates carry over.  After
+// the step the correspondences and the certificate records are read back (a wait per step: a
+// diagnostic entry), the records mapped from source tree slots to query order.
+int Engine::nn_sequence(const double* query, int64_t nq, const double* data, int64_t nd, int dim, double alpha,
+                        int n_steps, const double* poses, int restart_at, const NNSequenceOut& out) {
+    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
+    int rc = nn_setup(query, nq, data, nd, dim, alpha);
+    if (rc) return rc;
+    hipStream_t s = stream_;
+    constexpr size_t kStats = (size_t)kStatCols * kStatSlots;
+    HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStats, s));
+    const TreeBufs& tb = dim == 12 ? t12_ : t3_;
+    std::vector<int32_t> perm(nq), ci(nq);
+    std::vector<float> cd(nq);
+    std::vector<NNCert> cert(nq);
+    std::vector<unsigned long long> st(kStats);
+    HIPCHK(hipMemcpyAsync(perm.data(), tb.perm.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));  // (source cloud: slot 0 on)
+    const View v = view();
+    unsigned long long searched_before = 0;
+    PairDev& P = nn_pair_;
+    for (int k = 1; k <= n_steps; ++k) {
+        std::memcpy(P.T, poses + 16 * (size_t)(k - 1), sizeof(P.T));
+        P.iter = k;
+        P.phase_start = (restart_at > 0 && k >= restart_at) ? restart_at : 1;
+        HIPCHK(hipMemcpyAsync(d_pairs_.p, &P, sizeof(P), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync((double*)d_hist_.p + (size_t)(k % kHist) * 12, P.T, sizeof(P.T), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(d_flag_count_.p, 0, 3 * sizeof(int32_t), s));
+        HIPCHK(hipMemsetAsync(d_cls_.p, 0, sizeof(int32_t) * 2 * 8 * 16, s));
+        HIPCHK(hipMemsetAsync(d_rechecked_.p, 0, sizeof(int32_t), s));
+        launch_nn_prep(v, nullptr, s);
+        launch_nn(v, dim, s);
+        HIPCHK(hipGetLastError());
+        int32_t fc[3] = {0, 0, 0}, rech = 0;
+        HIPCHK(hipMemcpyAsync(ci.data(), d_corr_idx_.p, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cd.data(), d_corr_dist_.p, sizeof(float) * nq, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cert.data(), d_cert_.p, sizeof(NNCert) * nq, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(fc, d_flag_count_.p, sizeof(fc), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&rech, d_rechecked_.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(st.data(), d_stats_.p, sizeof(unsigned long long) * kStats, hipMemcpyDeviceToHost, s));
+        SYNC_STREAM(s);
+        // k_nn_prep's work counter of the phase: queries it left to the search, summed over the slots
+        unsigned long long searched = 0;
+        for (int r = 0; r < kStatSlots; ++r) searched += st[(size_t)kStatCols * r + (dim == 12 ? 5 : 7)];
+        const size_t row = (size_t)(k - 1) * nq;
+        for (int64_t i = 0; i < nq; ++i)
+            if (ci[i] < 0 || ci[i] >= nd) return SE3ICP_ERR_INTERNAL;
+        for (int64_t x = 0; x < nq; ++x)
+            if (perm[x] < 0 || perm[x] >= nq) return SE3ICP_ERR_INTERNAL;
+        if (out.idx) std::memcpy(out.idx + row, ci.data(), sizeof(int32_t) * nq);
+        if (out.dist) std::memcpy(out.dist + row, cd.data(), sizeof(float) * nq);
+        for (int64_t x = 0; x < nq; ++x) {
+            const size_t at = row + perm[x];
+            if (out.cert_d1) out.cert_d1[at] = cert[x].d1;
+            if (out.cert_l2) out.cert_l2[at] = cert[x].l2;
+            if (out.cert_iter) out.cert_iter[at] = cert[x].iter;
+            if (out.cert_j) out.cert_j[at] = cert[x].j;
+        }
+        if (out.searched) out.searched[k - 1] = (int32_t)(searched - searched_before);
+        if (out.single) out.single[k - 1] = fc[dim == 12 ? 1 : 2];
+        if (out.rechecked) out.rechecked[k - 1] = rech;
+        searched_before = searched;
     }
     return 0;
 }

@@ -151,6 +151,17 @@ class Engine {
     int estimate_normals(const double* xyz, int64_t n, int k, double* normals);
     int nn(const double* query, int64_t nq, const double* data, int64_t nd, int dim, int32_t* idx, double* d2,
            int32_t* num_rechecked);
+    // the loop's k_nn_prep and search over a given pose sequence (se3icp_nn_sequence); the caller
+    // has validated the arguments.  Any output may be null.
+    struct NNSequenceOut {
+        int32_t* idx;
+        float* dist;
+        float *cert_d1, *cert_l2;
+        int32_t *cert_iter, *cert_j;
+        int32_t *searched, *single, *rechecked;
+    };
+    int nn_sequence(const double* query, int64_t nq, const double* data, int64_t nd, int dim, double alpha,
+                    int n_steps, const double* poses, int restart_at, const NNSequenceOut& out);
 
     // Voxel-grid downsample of nclouds clouds resident in HBM (cloud c: points off[c] .. off[c+1]
     // of d_xyz, voxel size vs[c]) into d_out, compacted and contiguous; out_off [nclouds + 1] on
@@ -178,6 +189,7 @@ class Engine {
     template <class T>
     T* ensure(DevBuf& b, size_t count);
     int alloc_points(int64_t ntot, int kmax, bool knn_list = false);
+    int nn_setup(const double* query, int64_t nq, const double* data, int64_t nd, int dim, double alpha);
     // build the D-dimensional kd-trees of every cloud over `vec` ([D][ld] f32).  role (null:
     // every cloud builds) says per cloud kTreeBuilds, kTreeAbsent or the cloud whose finished
     // order it adopts (tree.hpp); tab is the table's home on the host and the device until the
@@ -322,6 +334,11 @@ class Engine {
         // the report's sums and per-point staging
         d_rep_partial_{bufs_}, d_rep_out_{bufs_}, d_rep_off_{bufs_}, d_rep_idx_{bufs_}, d_rep_dist_{bufs_};
     TreeBufs t3_{bufs_}, t12_{bufs_};
+    // nn_setup: the host SoA staging of the NN stage entries and their pair record
+    std::vector<double> nn_m64_;
+    std::vector<float> nn_m32_;
+    std::vector<int32_t> nn_cof_;
+    PairDev nn_pair_{};
     // register_graph: the distinct clouds' raw columns and confidences (swapped with xyz64 /
     // conf64 between the call's two layouts), the segment and chunk tables of the k_graph kernels
     DevBuf g_raw_xyz_{bufs_}, g_raw_conf_{bufs_}, g_seg_{bufs_}, g_chunks_{bufs_};

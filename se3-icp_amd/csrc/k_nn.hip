@@ -376,15 +376,9 @@ __device__ __forceinline__ void pose_m0(const double* T, const double* m, double
 //   |T M0 - T' M0|^2 = alpha^2 |(R - R') X|_F^2 + |(R - R') m_t + t - t'|^2
 //                    = alpha^2 |R - R'|_F^2     + |(R - R') m_t + t - t'|^2
 // and |T M0|^2 = 3 alpha^2 + |R m_t + t|^2 (X orthonormal to f64 rounding; padded below).
-// The 3-D phase is the translation part alone (alpha = 0).
-__device__ __forceinline__ double rot_frob2(const double* A, const double* B) {
-    double s = 0.0;
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) s += (A[r * 4 + c] - B[r * 4 + c]) * (A[r * 4 + c] - B[r * 4 + c]);
-    return s;
-}
+// The 3-D phase is the translation part alone (alpha = 0).  (rot_frob2, the displacement bound
+// and the settle predicate: nn_cert.hpp, tested on the host.)
+using nncert::rot_frob2;
 __device__ __forceinline__ double dist3_f64(const double* a, const double* b) {
     return sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
 }
@@ -405,7 +399,7 @@ __device__ __forceinline__ bool prep_settle(const View& v, const TreeRef& TR, co
     const float4 c0 = reinterpret_cast<const float4*>(cp)[0];
     const int ci = __float_as_int(c0.z);
     const double qn = sqrt(rot2 + Qt[0] * Qt[0] + Qt[1] * Qt[1] + Qt[2] * Qt[2]);
-    if ((int)(ci >= P->phase_start) & (int)(ci < it) & (int)(it - ci < kHist)) {
+    if (nncert::cert_usable(ci, it, P->phase_start)) {
         double Tr[12], Qr[3];
         load_hist(v, ci, pair, Tr);
         pose_point(Tr, mt[0], mt[1], mt[2], Qr);
@@ -413,11 +407,9 @@ __device__ __forceinline__ bool prep_settle(const View& v, const TreeRef& TR, co
         const double dt = dist3_f64(Qt, Qr);
         // |q_now - q_then|, padded for the frame's orthonormality and the rounding of the
         // two f64 queries the searches used
-        const double dl = sqrt(a2 * rot_frob2(T, Tr) * (1.0 + 1e-12) + dt * dt) * (1.0 + 1e-12) + 2e-15 * (qn + qr);
-        const double a = (double)c0.y - dl, b = (double)c0.x + dl;
-        // margin for the f64 rounding of the reference's own squared distances (|q| + |target| <= M)
-        const double M = 2.0 * qn + b;
-        if ((int)(a > b) & (int)((a - b) * (a + b) > 1e-14 * M * M)) {
+        const double dl = nncert::settle_dl(a2, T, Tr, dt, qn, qr);
+        // (with a margin for the f64 rounding of the reference's own squared distances)
+        if (nncert::settle_holds(c0.x, c0.y, dl, qn)) {
             // settled: corr_idx[g] (= the record's j) stays; the distance to its anchor
             const double t[3] = {cp->t[0], cp->t[1], cp->t[2]};
             v.corr_dist[g] = anchor_dist(Qt, t);
@@ -689,8 +681,8 @@ __device__ __forceinline__ void nn_finish(const View& v, const PairDev* P, int p
     match_anchor(v, D == 12 ? PHASE_SE3 : PHASE_R3, ct, j, t);
     v.corr_dist[g] = anchor_dist(Qt, t);
     if (!nocert) {
-        const float l2 = fminf(d2 - f32_err(d2, na, nb, D), thr * (1.f - 4e-6f));
-        cw[0] = make_float4(sqrtf(d1 + f32_err(d1, na, nb, D)) * (1.f + 1e-6f), sqrtf(fmaxf(l2, 0.f)) * (1.f - 1e-6f),
+        const float l2 = nncert::cert_l2_sq(d2, thr, na, nb, D);
+        cw[0] = make_float4(nncert::cert_d1(d1, na, nb, D), nncert::cert_l2_root(l2),
                             __int_as_float(P->iter), __int_as_float(j));
         double* tw = reinterpret_cast<double*>(cw + 1);
         tw[0] = t[0];
@@ -803,9 +795,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D == 12 ? kW
         // pruning threshold for the best / second-best f32 distances a1 <= a2: the certified
         // radius a1 + 3 err, widened by the margin up to (sqrt(a1) + 2 mrg)^2 but never past a2
         auto widen = [&](float a1, float a2) __attribute__((always_inline)) {
-            const float e = sqrtf(a1) + 2.f * mrg;
-            const float t = fmaxf(a1, fminf(e * e, a2));
-            return t + 3.f * f32_err(t, na, nb, D);
+            return nncert::widen_radius(a1, a2, mrg, na, nb, D);
         };
         float d1 = INFINITY, d2 = INFINITY;
         int i1 = -1;  // target tree position of the best candidate
@@ -1119,9 +1109,7 @@ __device__ __forceinline__ void single_one(const View& v, const PairDev* P, int 
     for (int r = 0; r < D / 2; ++r) q2[r] = f32x2{q[2 * r], q[2 * r + 1]};
     const float mrg = tp_pre == -2 ? v.cert[gx].margin : mrg_pre;
     auto widen = [&](float a1, float a2) __attribute__((always_inline)) {
-        const float e = sqrtf(a1) + 2.f * mrg;
-        const float t = fmaxf(a1, fminf(e * e, a2));
-        return t + 3.f * f32_err(t, na, nb, D);
+        return nncert::widen_radius(a1, a2, mrg, na, nb, D);
     };
     const float* tv = TR.tvec + tree_tv_ix<D>(0, ct.off, 0);  // (the cloud's first slot)
     const size_t ld = v.ld;

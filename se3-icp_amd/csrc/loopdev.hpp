@@ -6,6 +6,7 @@
 #include <climits>
 #include <cmath>
 
+#include "nn_cert.hpp"
 #include "tree.hpp"
 #include "view.hpp"
 #include "wave.hpp"
@@ -49,14 +50,8 @@ __device__ __forceinline__ void query_f64(const View& v, const double* T, int g,
     }
 }
 
-// Rigorous bound on |f32 squared distance - exact squared distance of the f64 vectors|
-// (DESIGN.md "Certified f32 arg-min"): both vectors rounded to f32 (u = 2^-24), D
-// differences and a D-term FMA chain; na, nb bound the two vector norms.
-__device__ __forceinline__ float f32_err(float d, float na, float nb, int D) {
-    const float u = 5.9604645e-08f;
-    const float s = na + nb;
-    return 1.25f * (2.f * u * s * sqrtf(fmaxf(d, 0.f)) + (float)(D + 3) * u * d + 4.f * u * u * s * s) + 1e-30f;
-}
+// the f32 error bound of a squared distance (nn_cert.hpp, tested on the host)
+using nncert::f32_err;
 
 // nanoflann L2_Adaptor::evalMetric order (groups of 4), no FMA contraction
 __device__ __forceinline__ double l2_nanoflann12(const double* a, const double* b) {

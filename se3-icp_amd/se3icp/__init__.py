@@ -10,7 +10,7 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            cli_params,
                            estimate_normals,
                            kitti_params, knn_self, last_kernel_times, set_nn_events, set_profiling, lounge_params,
-                           nearest_neighbors,
+                           nearest_neighbors, nearest_neighbors_sequence,
                            register_batch, register_batch_device, register_batch_traced, setup_record, toldi_frames,
                            alpha_grid, register_sweep, register_sweep_device, register_sweep_traced, sweep_params,
                            PairReport, register_batch_report, register_batch_report_device, register_sweep_report,
@@ -25,7 +25,7 @@ from ._lib import Report, ReportOptions  # noqa: F401
 
 __all__ = [
     "IterativeSE3Registration", "register_batch", "register_batch_device", "DeviceBatchRunner", "PipelinedBatchRunner", "register_batch_traced", "toldi_frames", "knn_self",
-    "estimate_normals", "nearest_neighbors", "default_params", "cli_params", "kitti_params", "lounge_params",
+    "estimate_normals", "nearest_neighbors", "nearest_neighbors_sequence", "default_params", "cli_params", "kitti_params", "lounge_params",
     "read_ply_xyz", "write_ply_xyz", "METHODS", "Se3IcpError",
     "register_sweep", "register_sweep_device", "register_sweep_traced", "alpha_grid", "sweep_params",
     "PairReport", "Report", "ReportOptions", "register_batch_report", "register_batch_report_device",

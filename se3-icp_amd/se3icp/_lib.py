@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_register_sweep_report", "se3icp_register_sweep_report_device",
     "se3icp_request_report", "se3icp_get_report",
     "se3icp_toldi_frames", "se3icp_knn_self", "se3icp_estimate_normals", "se3icp_nn",
+    "se3icp_nn_sequence_version", "se3icp_nn_sequence",
     "se3icp_synthetic_pairs", "se3icp_synthetic_reference", "se3icp_synthetic_reference_device",
     "se3icp_random_downsample",
     "se3icp_voxel_version", "se3icp_voxel_downsample_device", "se3icp_voxel_downsample",
@@ -266,6 +267,11 @@ def load():
     L.se3icp_knn_self.argtypes = [C.c_int, dp, C.c_int64, C.c_int, ip]
     L.se3icp_estimate_normals.argtypes = [C.c_int, dp, C.c_int64, C.c_int, dp]
     L.se3icp_nn.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, ip, dp, ip]
+    if hasattr(L, "se3icp_nn_sequence"):  # (SE3ICP_LIB may name an older build for an A/B run)
+        fp = C.POINTER(C.c_float)
+        L.se3icp_nn_sequence_version.restype = C.c_int
+        L.se3icp_nn_sequence.argtypes = [C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int, C.c_double, C.c_int32, dp,
+                                         C.c_int32, ip, fp, fp, fp, ip, ip, ip, ip, ip]
     L.se3icp_synthetic_pairs.restype = C.c_int64
     L.se3icp_synthetic_pairs.argtypes = [C.c_int, dp, C.c_int64, C.c_int32, dp, C.c_double, C.c_double, C.c_uint64,
                                          vp, vp, C.c_int]

@@ -989,6 +989,32 @@ def nearest_neighbors(query, data, device: int = 0):
     return idx, d2, int(nr.value)
 
 
+def nearest_neighbors_sequence(query, data, poses, alpha: float = 1.0, restart_at: int = 0, device: int = 0) -> dict:
+    """The loop's NN stage over a given pose sequence (se3icp_nn_sequence): step k (1-based) is
+    iteration k of a one-pair run whose pose is poses[k - 1] ((n_steps, 4, 4) or (n_steps, 16),
+    row-major).  query (nq, dim), data (nd, dim), dim 3 or 12; a 12-D query row is
+    [alpha x, alpha y, alpha z, t] with (x y z) orthonormal (not checked).  Returns per step and
+    query (n_steps, nq) `idx`, `dist` (f32), `cert_d1`, `cert_l2` (f32), `cert_iter`, `cert_j`, and
+    per step `searched`, `single`, `rechecked`."""
+    q = np.ascontiguousarray(query, dtype=np.float64)
+    d = np.ascontiguousarray(data, dtype=np.float64)
+    T = np.ascontiguousarray(poses, dtype=np.float64)
+    if q.ndim != 2 or d.ndim != 2 or q.shape[1] != d.shape[1] or T.size % 16 or T.ndim < 2:
+        raise _lib.Se3IcpError(_lib.ERR_INVALID_ARG, "nn_sequence: shapes")
+    ns, nq = T.size // 16, q.shape[0]
+    out = {k: np.zeros((ns, nq), t) for k, t in (("idx", np.int32), ("dist", np.float32), ("cert_d1", np.float32),
+                                                 ("cert_l2", np.float32), ("cert_iter", np.int32),
+                                                 ("cert_j", np.int32))}
+    out.update({k: np.zeros(ns, np.int32) for k in ("searched", "single", "rechecked")})
+    dp, ip, fp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float)
+    ptr = lambda k: out[k].ctypes.data_as(fp if out[k].dtype == np.float32 else ip)
+    _lib.check(_lib.load().se3icp_nn_sequence(
+        int(device), q.ctypes.data_as(dp), nq, d.ctypes.data_as(dp), d.shape[0], int(d.shape[1]), float(alpha), ns,
+        T.ctypes.data_as(dp), int(restart_at), ptr("idx"), ptr("dist"), ptr("cert_d1"), ptr("cert_l2"),
+        ptr("cert_iter"), ptr("cert_j"), ptr("searched"), ptr("single"), ptr("rechecked")), "nn_sequence")
+    return out
+
+
 def set_lrf_seeding(mode: int, device: int = 0) -> None:
     """How the classes of one cloud seed each other's neighbour selection on the engine behind
     `device` (se3icp_set_lrf_seeding): 0 a cloud's later classes start from its first class's

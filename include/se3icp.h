@@ -725,6 +725,75 @@ typedef struct se3icp_setup_record {
 int se3icp_setup_record_version(void);  /* 1 */
 int se3icp_set_setup_record(int device, se3icp_setup_record* rec);
 
+/* The kd-trees of ONE pair as the next call that builds trees on `device` leaves them for its
+ * searches (diagnostic, of the kind of se3icp_setup_record; the tests check the order, the
+ * tree-ordered vectors and every node box exactly).  Recorded are the 3-D and the 12-D tree of
+ * cloud slots 2 * pair (src) and 2 * pair + 1 (tgt), read back from the buffers the searches
+ * read, whichever kernels, adoption or sweep expansion filled them; a registration call takes
+ * the record where it takes the setup record (behind the 12-D build, before the first
+ * iteration), se3icp_nn / se3icp_nn_sequence behind their build (pair 0: src the queries, tgt
+ * the data; only the tree of `dim` exists).  One documented layout whatever the device's:
+ *   perm    [n] tree position -> point;  pos [n] point -> tree position;
+ *   vec     [n * D] the f32 input vectors in point order (3-D: the points minus f32_center);
+ *   tvec    [n * D] the f32 vectors in tree order;
+ *   tvec64  [n * 3] the f64 vectors in tree order: the points (3-D), the translation entries
+ *           9..11 of the rows (12-D);
+ *   tpt64   [n * 4] 3-D only: the (x, y, z, 0) records of the f64 points in tree order;
+ *   lo, hi  [nnodes * D] the node boxes in heap order (node i of level l: 2^l - 1 + i).
+ * `written` (SE3ICP_TREE_* bits) says which arrays the build produces for that tree and that
+ * were asked for; an array the build does not produce is left alone: a loop source's 12-D tree
+ * below depth 0 is its order and its f64 translation entries only, a 12-D target's has no f64
+ * vectors.  `exists` is 0 for a tree the call did not build (the 12-D trees of run_icp, the
+ * other dimension of se3icp_nn); its other outputs are then 0.  role: SE3ICP_TREE_BUILT, or the
+ * cloud slot whose finished order the slot adopted in the last build that touched it (a sweep's
+ * replicas show their base cloud's).  G: the levels the build splits with one grid over all
+ * clouds; H: how many of those, the first ones, took the multi-pass sequence (the others one
+ * workgroup per node); the levels below G are split by one workgroup per level-G node.
+ * Any array may be NULL; `cap` (points) and `node_cap` (nodes) say what the arrays have room
+ * for: a tree with more, for an array that is asked for, fails the call with
+ * SE3ICP_ERR_INVALID_ARG before its loop.  One-shot, for the next such call on that engine
+ * (device | slot << 8); the pointers are kept until that call returns; NULL disarms; a pair
+ * outside the call's results is SE3ICP_ERR_INVALID_ARG from that call.  The arguments are
+ * checked before the device is looked up.  May be armed together with a setup record.  Armed,
+ * the call waits for the device before its loop; unarmed, a call queues exactly what it queues
+ * without this entry.  Never used by bench.py. */
+#define SE3ICP_TREE_PERM 1
+#define SE3ICP_TREE_POS 2
+#define SE3ICP_TREE_VEC 4
+#define SE3ICP_TREE_TVEC 8
+#define SE3ICP_TREE_TVEC64 16
+#define SE3ICP_TREE_TPT64 32
+#define SE3ICP_TREE_BOXES 64
+#define SE3ICP_TREE_BUILT (-1)
+typedef struct se3icp_tree_side {
+    int32_t* perm;          /* [cap] */
+    int32_t* pos;           /* [cap] */
+    float* vec;             /* [cap * D] */
+    float* tvec;            /* [cap * D] */
+    double* tvec64;         /* [cap * 3] */
+    double* tpt64;          /* [cap * 4] (3-D) */
+    float* lo;              /* [node_cap * D] */
+    float* hi;              /* [node_cap * D] */
+    int64_t cap;            /* points the arrays have room for */
+    int64_t node_cap;       /* nodes lo / hi have room for */
+    int64_t n;              /* out: points of the cloud */
+    int32_t exists;         /* out: 1 if the call built this tree */
+    int32_t D;              /* out: 3 or 12 */
+    int32_t L;              /* out: depth (leaves at level L) */
+    int32_t nnodes;         /* out: 2^(L+1) - 1 nodes */
+    int32_t G;              /* out: global levels of the build */
+    int32_t H;              /* out: multi-pass levels among them */
+    int32_t role;           /* out: SE3ICP_TREE_BUILT or the donor's cloud slot */
+    int32_t written;        /* out: SE3ICP_TREE_* bits of the arrays filled */
+} se3icp_tree_side;
+typedef struct se3icp_tree_record {
+    int32_t pair;           /* result index within the next call */
+    int32_t recorded;       /* out: 1 once the record was taken */
+    se3icp_tree_side src3, tgt3, src12, tgt12;
+} se3icp_tree_record;
+int se3icp_tree_record_version(void);  /* 1 */
+int se3icp_set_tree_record(int device, se3icp_tree_record* rec);
+
 /* Diagnostic: which kernels compute the setup's kNN / TOLDI / normals on `device`:
  *   0 = the default: eight queries per wavefront (k_lrf8), the exact one-query-per-wavefront
  *       kernel for the queries it hands over, the global-buffer kernel for k > 128;

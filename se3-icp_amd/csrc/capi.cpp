@@ -775,6 +775,21 @@ int se3icp_set_setup_record(int device, se3icp_setup_record* rec) {
     return 0;
 }
 
+int se3icp_tree_record_version(void) { return 1; }
+
+int se3icp_set_tree_record(int device, se3icp_tree_record* rec) {
+    if (rec) {  // (the arguments before the device: a bad record is reported on any machine)
+        if (rec->pair < 0) return SE3ICP_ERR_INVALID_ARG;
+        for (const se3icp_tree_side* t : {&rec->src3, &rec->tgt3, &rec->src12, &rec->tgt12})
+            if (t->cap < 0 || t->node_cap < 0) return SE3ICP_ERR_INVALID_ARG;
+    }
+    Engine* e = usable_engine(device);
+    if (!e) return SE3ICP_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(e->mutex());
+    e->set_tree_record(rec);
+    return 0;
+}
+
 int se3icp_set_lrf_exact(int device, int exact_only) {
     Engine* e = usable_engine(device);
     if (!e) return SE3ICP_ERR_NO_DEVICE;

@@ -365,8 +365,20 @@ int Engine::build_tree(int D, const float* vec, hipStream_t s, const double* vec
     }
     tree_stats_[D == 12 ? 2 : 0] += nbuild;
     tree_stats_[D == 12 ? 3 : 1] += nadopt;
-    if (build_trees(t, d_sort_tmp_.p, d_sort_tmp_.bytes, (uint32_t*)d_keys0_.p, (int32_t*)d_vals1_.p, s) != 0)
+    int levels[2] = {0, 0};  // G and H as build_trees launched them
+    if (build_trees(t, d_sort_tmp_.p, d_sort_tmp_.bytes, (uint32_t*)d_keys0_.p, (int32_t*)d_vals1_.p, s, levels) != 0)
         return SE3ICP_ERR_HIP;
+    {
+        // what this build is for every slot it touches (se3icp_set_tree_record)
+        std::vector<TreeLog>& log = tree_log_[D == 12];
+        if ((int)log.size() != nclouds_) log.assign(nclouds_, TreeLog{});
+        const int G = levels[0], H = levels[1];
+        auto role_of = [&](int c) { return nbuild != nclouds_ ? (*role)[c] : kTreeBuilds; };
+        for (int c = 0; c < nclouds_; ++c)
+            if (role_of(c) == kTreeBuilds) log[c] = TreeLog{kTreeBuilds, tb.L, G, H};
+        for (int c = 0; c < nclouds_; ++c)  // an adopter's order took its donor's path
+            if (role_of(c) >= 0) log[c] = TreeLog{role_of(c), tb.L, G, log[role_of(c)].H};
+    }
     return 0;
 }
 
@@ -670,6 +682,9 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     trace_ = nullptr;
     se3icp_setup_record* sr = c->sr = setup_rec_;  // one-shot likewise
     setup_rec_ = nullptr;
+    se3icp_tree_record* tk = c->tr_rec = tree_rec_;  // and the tree record
+    tree_rec_ = nullptr;
+    for (std::vector<TreeLog>& log : tree_log_) log.clear();
     pose_raw_.clear();  // (a call without a posed edge plans its seeds over clouds)
     pose_rigid_.clear();
     if (args) return args;
@@ -682,6 +697,13 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
         sr->recorded = 0;
         sr->src.n = sr->tgt.n = 0;
         sr->src.written = sr->tgt.written = 0;
+    }
+    if (tk) {
+        if (tk->pair < 0 || (int64_t)tk->pair >= nslots) return SE3ICP_ERR_INVALID_ARG;
+        for (const se3icp_tree_side* t : {&tk->src3, &tk->tgt3, &tk->src12, &tk->tgt12})
+            if (t->cap < 0 || t->node_cap < 0) return SE3ICP_ERR_INVALID_ARG;
+        c->tr_pair = tk->pair;
+        tk->recorded = 0;
     }
     if (rest) return rest;
     HIPCHK(hipSetDevice(dev_));
@@ -727,6 +749,13 @@ int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const
     // these are the arrays the loop consumes.  Unarmed, nothing is queued here.
     if (c.sr) {
         rc = record_setup(c.sr, c.sr_pair, s);
+        if (rc) return rc;
+    }
+    // The armed tree record, at the same point: both trees of the pair's slots are complete
+    // (the 3-D ones of the setup, a sweep's replicas, the 12-D ones above) and the loop only
+    // reads them.
+    if (c.tr_rec) {
+        rc = record_trees(c.tr_rec, c.tr_pair, s);
         if (rc) return rc;
     }
     const ReportReq rq{ropts, reports};
@@ -1579,6 +1608,13 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
             gcall.sr = call.sr;
             gcall.sr_pair = call.sr_pair - v0 * P;
         }
+        // and the armed tree record: the replicas' 3-D trees are copies of their base clouds'
+        if (call.tr_rec && call.tr_pair >= v0 * P && call.tr_pair < (v0 + g) * P) {
+            gcall.tr_rec = call.tr_rec;
+            gcall.tr_pair = call.tr_pair - v0 * P;
+            tree_log_[0].resize(nclouds_);
+            for (int c = nbase; c < nclouds_; ++c) tree_log_[0][c] = tree_log_[0][c % nbase];
+        }
         rc = run_pairs(mp, g * P, vns.data(), vnt.data(), variants + v0, P, true, gcall, out + (size_t)v0 * P,
                        ropts, reports ? reports + (size_t)v0 * P : nullptr);
         if (use) tr->iters_recorded = gtr.iters_recorded;
@@ -1961,6 +1997,100 @@ int Engine::record_setup(se3icp_setup_record* rec, int pair, hipStream_t s) {
     return 0;
 }
 
+// The armed tree record of pair `pair` (cloud slots 2 * pair, 2 * pair + 1 of the current
+// layout): per slot and dimension the scalars of the last build that touched the slot
+// (tree_log_), then the arrays the searches read, from the device's layouts (tree.hpp: 3-D
+// columns [3][ld], 12-D rows [ld][12], boxes [nclouds][2^(L+1)][D]) into [n][D].  `written`
+// follows the kernels: a loop source's 12-D tree below depth 0 is order only (k_tree_local's
+// order_only; at depth 0 k_tree_finish and k_tree_leafbox write every cloud alike), the f64
+// 12-D vectors are the sources'.  Called with the builds queued and no loop work behind them.
+int Engine::record_trees(se3icp_tree_record* rec, int pair, hipStream_t s) {
+    if (pair < 0 || 2 * pair + 1 >= nclouds_) return SE3ICP_ERR_INVALID_ARG;
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t ld = (size_t)ld_;
+    std::vector<float> f32;
+    std::vector<double> f64;
+    for (int k = 0; k < 4; ++k) {
+        const int side = k & 1, D = k < 2 ? 3 : 12;
+        se3icp_tree_side& o = *(k == 0 ? &rec->src3 : k == 1 ? &rec->tgt3 : k == 2 ? &rec->src12 : &rec->tgt12);
+        const int c = 2 * pair + side;
+        const std::vector<TreeLog>& log = tree_log_[D == 12];
+        o.n = 0;
+        o.exists = o.D = o.L = o.nnodes = o.G = o.H = o.role = o.written = 0;
+        if ((int)log.size() != nclouds_ || log[c].role == kTreeAbsent) continue;
+        const TreeLog& lg = log[c];
+        const TreeBufs& tb = D == 12 ? t12_ : t3_;
+        const CloudDev& cd = h_clouds_[c];
+        const size_t n = (size_t)cd.n, off = (size_t)cd.off;
+        const size_t slots = (size_t)2 << lg.L, nodes = slots - 1;
+        o.n = cd.n;
+        o.exists = 1;
+        o.D = D;
+        o.L = lg.L;
+        o.nnodes = (int32_t)nodes;
+        o.G = lg.G;
+        o.H = lg.H;
+        o.role = lg.role;
+        const bool order_only = D == 12 && side == 0 && lg.L > 0;
+        const bool has64 = D == 3 || side == 0;
+        if ((int64_t)cd.n > o.cap && (o.perm || o.pos || o.vec || o.tvec || o.tvec64 || o.tpt64)) return SE3ICP_ERR_INVALID_ARG;
+        if ((int64_t)nodes > o.node_cap && (o.lo || o.hi)) return SE3ICP_ERR_INVALID_ARG;
+        int32_t written = 0;
+        auto get = [&](void* dst, const void* src, size_t bytes) -> int {
+            HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            return 0;
+        };
+        // [D][ld] f32 columns or [ld][12] rows of the cloud's n slots from `base` into out [n][D]
+        auto vectors = [&](const void* base, float* out) -> int {
+            if (D == 12) return get(out, (const float*)base + 12 * off, sizeof(float) * 12 * n);
+            f32.resize(3 * n);
+            for (int a = 0; a < 3; ++a)
+                if (int rc = get(f32.data() + a * n, (const float*)base + a * ld + off, sizeof(float) * n)) return rc;
+            for (size_t i = 0; i < n; ++i)
+                for (int a = 0; a < 3; ++a) out[3 * i + a] = f32[a * n + i];
+            return 0;
+        };
+        int rc = 0;
+        if (o.perm) {
+            if ((rc = get(o.perm, (const int32_t*)tb.perm.p + off, sizeof(int32_t) * n))) return rc;
+            written |= SE3ICP_TREE_PERM;
+        }
+        if (o.pos && !order_only) {
+            if ((rc = get(o.pos, (const int32_t*)tb.pos.p + off, sizeof(int32_t) * n))) return rc;
+            written |= SE3ICP_TREE_POS;
+        }
+        if (o.vec) {
+            if ((rc = vectors(D == 12 ? d_fr32_.p : d_xyz32_.p, o.vec))) return rc;
+            written |= SE3ICP_TREE_VEC;
+        }
+        if (o.tvec && !order_only) {
+            if ((rc = vectors(tb.vec.p, o.tvec))) return rc;
+            written |= SE3ICP_TREE_TVEC;
+        }
+        if (o.tvec64 && has64 && tb.vec64.p) {
+            f64.resize(3 * n);
+            for (int a = 0; a < 3; ++a)
+                if ((rc = get(f64.data() + a * n, (const double*)tb.vec64.p + a * ld + off, sizeof(double) * n))) return rc;
+            for (size_t i = 0; i < n; ++i)
+                for (int a = 0; a < 3; ++a) o.tvec64[3 * i + a] = f64[a * n + i];
+            written |= SE3ICP_TREE_TVEC64;
+        }
+        if (o.tpt64 && D == 3 && tb.vec64a.p) {
+            if ((rc = get(o.tpt64, (const double4*)tb.vec64a.p + off, sizeof(double4) * n))) return rc;
+            written |= SE3ICP_TREE_TPT64;
+        }
+        if ((o.lo || o.hi) && !order_only) {
+            const size_t at = (size_t)c * slots * D;
+            if (o.lo && (rc = get(o.lo, (const float*)tb.lo.p + at, sizeof(float) * nodes * D))) return rc;
+            if (o.hi && (rc = get(o.hi, (const float*)tb.hi.p + at, sizeof(float) * nodes * D))) return rc;
+            if (o.lo && o.hi) written |= SE3ICP_TREE_BOXES;
+        }
+        o.written = written;
+    }
+    rec->recorded = 1;
+    return 0;
+}
+
 // ----------------------------------------------------------------------------- stage entry points
 int Engine::knn_self(const double* xyz, int64_t n, int k, int32_t* idx) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
@@ -2104,8 +2234,17 @@ int Engine::nn_setup(const double* query, int64_t nq, const double* data, int64_
     HIPCHK(hipMemcpyAsync(dst32, m32.data(), sizeof(float) * m32.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_cloud_of_.p, cof.data(), sizeof(int32_t) * L, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_clouds_.p, h_clouds_.data(), sizeof(CloudDev) * 2, hipMemcpyHostToDevice, s));
+    for (std::vector<TreeLog>& log : tree_log_) log.clear();
+    se3icp_tree_record* tk = tree_rec_;  // one-shot, as a registration call's
+    tree_rec_ = nullptr;
+    if (tk && tk->pair != 0) return SE3ICP_ERR_INVALID_ARG;
+    if (tk) tk->recorded = 0;
     rc = build_tree(dim, dst32, s, dst64);
     if (rc) return rc;
+    if (tk) {
+        rc = record_trees(tk, 0, s);
+        if (rc) return rc;
+    }
     rc = setup_chunks(1, s);
     if (rc) return rc;
     PairDev& P = nn_pair_;

@@ -91,6 +91,7 @@ class Engine {
     void set_profiling(bool on) { profile_ = on; }
     void set_trace(se3icp_trace* t) { trace_ = t; }
     void set_setup_record(se3icp_setup_record* r) { setup_rec_ = r; }
+    void set_tree_record(se3icp_tree_record* r) { tree_rec_ = r; }
     void set_lrf_exact(int mode) { lrf_exact_only_ = mode; }
     void set_nn_events(bool on) { nn_events_ = on; }
     void set_batch_sharing(int level) { batch_sharing_ = level; }
@@ -217,6 +218,8 @@ class Engine {
         hipStream_t s = nullptr;
         se3icp_setup_record* sr = nullptr;
         int sr_pair = -1;
+        se3icp_tree_record* tr_rec = nullptr;  // the armed tree record, taken and remapped as sr is
+        int tr_pair = -1;
     };
     int open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c);
     // The clouds back to back in the SoA columns: offsets, chunk list, inputs (uploaded, or
@@ -308,6 +311,15 @@ class Engine {
     int record_trace(se3icp_trace* tr, int it, int& phase_of_it, hipStream_t s);
     se3icp_setup_record* setup_rec_ = nullptr;  // armed setup record of one pair (se3icp_set_setup_record)
     int record_setup(se3icp_setup_record* rec, int pair, hipStream_t s);
+    // The armed tree record of one pair (se3icp_set_tree_record) and, per dimension (0: 3-D,
+    // 1: 12-D) and cloud slot, what the call's last build that touched the slot was: host
+    // bookkeeping of build_tree, cleared by open_call and nn_setup.
+    struct TreeLog {
+        int32_t role = -2, L = 0, G = 0, H = 0;  // (-2: kTreeAbsent, no build of this call touched it)
+    };
+    se3icp_tree_record* tree_rec_ = nullptr;
+    std::vector<TreeLog> tree_log_[2];
+    int record_trees(se3icp_tree_record* rec, int pair, hipStream_t s);
     double trace_prev_[kStatCols] = {};
     std::vector<CloudDev> h_clouds_;
     std::vector<CloudSetup> h_setup_;

@@ -943,11 +943,14 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
 #endif
                 for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
 #if SE3ICP_TREE_LDS_SAMPLE && SE3ICP_TREE_EMPTY_FALLBACK
-                if (cnt == 0) {
-                    // (wave-uniform) a sub-node holding none of the fixed sample points -- deep
-                    // levels, small nodes: its own points from the columns, every one of them
-                    // (round 5 split such a sub-node on dimension 0 with mean = sd = 0, i.e. by
-                    // index)
+                if (cnt <= 1) {
+                    // (wave-uniform) a sub-node holding none of the fixed sample points, or one
+                    // (every variance 0: dimension 0 whatever the points) -- deep levels, small
+                    // nodes: its own points from the columns, every one of them (round 5 split
+                    // such a sub-node on dimension 0 with mean = sd = 0, i.e. by index)
+                    cnt = 0;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) { s1[d] = 0.f; s2[d] = 0.f; }
                     for (int e = a0 + lane; e < a1; e += 64) {
                         const int p = s_val[e];
                         ++cnt;
@@ -989,8 +992,8 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
         if (sort_per != 0) {
             // small sub-nodes: one wave sorts each in registers, in a network of the sub-node's
             // size (128, 256 or 512 keys) over 32-bit keys: the split coordinate quantised to
-            // 20 bits over the sub-node's sample mean +- 8 sd | the level-G position (12 bits,
-            // which also orders ties).  Any order gives a valid balanced tree (the searches
+            // 20 bits over the sub-node's own extent of it | the level-G position (12 bits,
+            // which also orders ties; s_mu / s_sd serve the LDS partition below only).  Any order gives a valid balanced tree (the searches
             // are exact over the node boxes); this one keeps the split at the median.
             const int lane = tid & 63, wv = tid >> 6;
             auto wave_level = [&](auto per_tag) {
@@ -998,17 +1001,38 @@ __global__ __launch_bounds__(kLocalThreads) __attribute__((amdgpu_waves_per_eu(4
                 for (int k = wv; k < nsub; k += kLocalThreads / 64) {
                     const int a0 = tree_first(n, l, (i << r) + k) - A, a1 = tree_first(n, l, (i << r) + k + 1) - A;
                     const int bd = s_best[k];
-                    const float sd = s_sd[k], qlo = s_mu[k] - 8.f * sd;
-                    const float qs = sd > 0.f ? 1048575.f / (16.f * sd) : 0.f;
-                    unsigned key[PER];
+                    // the keys span the sub-node's own extent of the split coordinate (the wave
+                    // holds every value: two butterflies), so no key is clamped and the two sides
+                    // of the median overlap by less than one key step.  (Quantised over the
+                    // sample's mean +- 8 sd, a sub-node with ONE sample point had sd = 0 and
+                    // kept its index order, and one with two or three close sample points
+                    // clamped most of its keys: 2 - 12 of a tree's last-level nodes, found by
+                    // the tree record's split check)
+                    float xv[PER];
+                    int pv[PER];
+                    float xlo = INFINITY, xhi = -INFINITY;
 #pragma unroll
                     for (int u = 0; u < PER; ++u) {
                         const int e = a0 + lane * PER + u;
+                        pv[u] = e < a1 ? s_val[e] : -1;
+                        xv[u] = pv[u] >= 0 ? col0[bd * m + pv[u]] : NAN;
+                        xlo = fminf(xlo, xv[u]);  // (fminf / fmaxf skip a NaN)
+                        xhi = fmaxf(xhi, xv[u]);
+                    }
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) {
+                        xlo = fminf(xlo, xor_lane(xlo, o));
+                        xhi = fmaxf(xhi, xor_lane(xhi, o));
+                    }
+                    const float qlo = xlo, ext = xhi - xlo;
+                    const float qs = (ext > 0.f && ext < INFINITY) ? 1048575.f / ext : 0.f;
+                    unsigned key[PER];
+#pragma unroll
+                    for (int u = 0; u < PER; ++u) {
                         key[u] = ~0u;
-                        if (e < a1) {
-                            const int p = s_val[e];
-                            const float qf = fminf(fmaxf((col0[bd * m + p] - qlo) * qs, 0.f), 1048575.f);  // NaN -> 0
-                            key[u] = ((unsigned)qf << 12) | (unsigned)p;
+                        if (pv[u] >= 0) {
+                            const float qf = fminf(fmaxf((xv[u] - qlo) * qs, 0.f), 1048575.f);  // NaN -> 0
+                            key[u] = ((unsigned)qf << 12) | (unsigned)pv[u];
                         }
                     }
                     wave_sort_u32<PER>(key);
@@ -1442,7 +1466,7 @@ __global__ __launch_bounds__(256) void k_clear_words(uint32_t* p, size_t n) {
 }
 }  // namespace
 
-int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t* perm_alt, hipStream_t s) {
+int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t* perm_alt, hipStream_t s, int* levels) {
     const int nb = (t.npts + 255) / 256;
     const int nbs = (t.npts + 256 * kSplitSample - 1) / (256 * kSplitSample);
     const int gfill = std::max(nb, 64);
@@ -1468,6 +1492,7 @@ int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t
     // workgroup per 60k-point node left 7/8 of the CUs idle for 120 us; 3-D breaks even)
     const int wg_min = t.D == 12 ? 2 * kTreeWgMin : kTreeWgMin;
     while (H < G && (ncb << H) < wg_min) ++H;
+    if (levels) levels[0] = G, levels[1] = H;
     const int nblk = (t.npts + kPartElems - 1) / kPartElems;
     const int nhist = (t.npts + kHistElems - 1) / kHistElems;
     if (ncb > 0) {

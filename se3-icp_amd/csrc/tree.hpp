@@ -126,7 +126,10 @@ inline int tree_global_levels(int max_n, int L) {
 }
 
 // qbuf: [npts] u32 scratch, perm_alt: [npts] the second permutation buffer of the global levels
-int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t* perm_alt, hipStream_t s);
+// levels (may be null): [0] G, the global levels of this build, [1] H, how many of them took the
+// multi-pass path -- what was launched, for the tree record
+int build_trees(TreeView t, void* tmp, size_t tmp_bytes, uint32_t* qbuf, int32_t* perm_alt, hipStream_t s,
+                int* levels = nullptr);
 size_t tree_build_temp_bytes(int npts, int nclouds, int max_n, int L);
 void tree_prof_report();  // (SE3ICP_PROF builds: k_tree_local's phase timeline, then reset)
 

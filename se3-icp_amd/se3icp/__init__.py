@@ -12,6 +12,7 @@ from .registration import (DeviceBatchRunner, IterativeSE3Registration, PairResu
                            kitti_params, knn_self, last_kernel_times, set_nn_events, set_profiling, lounge_params,
                            nearest_neighbors, nearest_neighbors_sequence,
                            register_batch, register_batch_device, register_batch_traced, setup_record, toldi_frames,
+                           tree_record,
                            alpha_grid, register_sweep, register_sweep_device, register_sweep_traced, sweep_params,
                            PairReport, register_batch_report, register_batch_report_device, register_sweep_report,
                            register_sweep_report_device,
@@ -33,7 +34,7 @@ __all__ = [
     "register_graph", "register_sequence", "sequence_edges", "expand_edges", "register_graph_device",
     "register_graph_report", "register_graph_traced", "last_graph_stats",
     "set_batch_sharing", "set_lrf_seeding", "last_seed_stats", "set_tree_sharing", "last_tree_stats",
-    "set_lrf_taking", "last_take_stats", "setup_record",
+    "set_lrf_taking", "last_take_stats", "setup_record", "tree_record",
     "voxel_downsample", "voxel_downsample_device",
     "edge_inits", "transform_points", "transform_device", "set_pose_seeding", "last_init_stats",
 ]

@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "se3icp_transform_points", "se3icp_transform_device",
     "se3icp_set_profiling", "se3icp_last_kernel_times", "se3icp_last_kernel_times_n", "se3icp_set_trace", "se3icp_set_lrf_exact",
     "se3icp_set_nn_events", "se3icp_setup_record_version", "se3icp_set_setup_record",
+    "se3icp_tree_record_version", "se3icp_set_tree_record",
     # include/se3icp_cc.h: metrics and pose files of the benchmark drivers (host only)
     "se3icp_cc_rot_3d", "se3icp_cc_angular_error_so3", "se3icp_cc_angular_error_so3_alt",
     "se3icp_cc_error_filterreg", "se3icp_cc_rot2euler", "se3icp_cc_avg_eul_error",
@@ -167,6 +168,47 @@ class SetupRecord(C.Structure):
         ("recorded", C.c_int32),
         ("src", SetupSide),
         ("tgt", SetupSide),
+    ]
+
+
+TREE_PERM, TREE_POS, TREE_VEC, TREE_TVEC, TREE_TVEC64, TREE_TPT64, TREE_BOXES = 1, 2, 4, 8, 16, 32, 64
+TREE_BUILT = -1
+
+
+class TreeSide(C.Structure):
+    """se3icp_tree_side."""
+    _fields_ = [
+        ("perm", C.POINTER(C.c_int32)),
+        ("pos", C.POINTER(C.c_int32)),
+        ("vec", C.POINTER(C.c_float)),
+        ("tvec", C.POINTER(C.c_float)),
+        ("tvec64", C.POINTER(C.c_double)),
+        ("tpt64", C.POINTER(C.c_double)),
+        ("lo", C.POINTER(C.c_float)),
+        ("hi", C.POINTER(C.c_float)),
+        ("cap", C.c_int64),
+        ("node_cap", C.c_int64),
+        ("n", C.c_int64),
+        ("exists", C.c_int32),
+        ("D", C.c_int32),
+        ("L", C.c_int32),
+        ("nnodes", C.c_int32),
+        ("G", C.c_int32),
+        ("H", C.c_int32),
+        ("role", C.c_int32),
+        ("written", C.c_int32),
+    ]
+
+
+class TreeRecord(C.Structure):
+    """se3icp_tree_record."""
+    _fields_ = [
+        ("pair", C.c_int32),
+        ("recorded", C.c_int32),
+        ("src3", TreeSide),
+        ("tgt3", TreeSide),
+        ("src12", TreeSide),
+        ("tgt12", TreeSide),
     ]
 
 
@@ -295,6 +337,9 @@ def load():
     if hasattr(L, "se3icp_setup_record_version"):  # (SE3ICP_LIB may name an older build for an A/B run)
         L.se3icp_setup_record_version.restype = C.c_int
         L.se3icp_set_setup_record.argtypes = [C.c_int, C.POINTER(SetupRecord)]
+    if hasattr(L, "se3icp_tree_record_version"):  # (likewise)
+        L.se3icp_tree_record_version.restype = C.c_int
+        L.se3icp_set_tree_record.argtypes = [C.c_int, C.POINTER(TreeRecord)]
     L.se3icp_set_lrf_exact.argtypes = [C.c_int, C.c_int]
     L.se3icp_set_nn_events.argtypes = [C.c_int, C.c_int]
     # (se3icp_set_batch_sharing(int, int), se3icp_set_lrf_seeding(int, int),

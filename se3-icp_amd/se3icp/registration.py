@@ -504,6 +504,63 @@ def setup_record(pair: int, n_src: int, n_tgt: int, device: int = 0):
         out[name] = d
 
 
+_TREE_BITS = {"perm": _lib.TREE_PERM, "pos": _lib.TREE_POS, "vec": _lib.TREE_VEC, "tvec": _lib.TREE_TVEC,
+              "tvec64": _lib.TREE_TVEC64, "tpt64": _lib.TREE_TPT64, "lo": _lib.TREE_BOXES, "hi": _lib.TREE_BOXES}
+
+
+@contextlib.contextmanager
+def tree_record(pair: int, n_src: int, n_tgt: int, device: int = 0, n_max: int | None = None):
+    """Arm the tree record (se3icp_set_tree_record) of result slot `pair` -- a source of n_src and
+    a target of n_tgt points -- for the one call made inside the block: any register_* entry, or
+    nearest_neighbors / nearest_neighbors_sequence (pair 0: the queries and the data).  n_max: the
+    largest cloud of the call (default: the larger of the two), which sets the trees' depth and so
+    the room the boxes need.  The dict it yields holds, after the block, under "src3", "tgt3",
+    "src12", "tgt12" None for a tree the call did not build, otherwise a dict of the scalars n, D,
+    L, nnodes, G, H, role (-1: built, else the donor's cloud slot), written, and the arrays perm
+    (n,), pos (n,), vec (n, D), tvec (n, D), tvec64 (n, 3), tpt64 (n, 4), lo / hi (nnodes, D) --
+    None where the build does not produce the array for that tree."""
+    L = _lib.load()
+    rec = _lib.TreeRecord()
+    rec.pair = int(pair)
+    n_max = max(int(n_src), int(n_tgt), int(n_max or 0), 1)
+    depth = 0
+    while (n_max + (1 << depth) - 1) >> depth > 64:  # tree_depth_for (tree.hpp)
+        depth += 1
+    nodes = (2 << depth) - 1
+    ptr = {np.dtype(np.int32): C.POINTER(C.c_int32), np.dtype(np.float32): C.POINTER(C.c_float),
+           np.dtype(np.float64): _DP}
+    bufs = {}
+    for name, n, D in (("src3", int(n_src), 3), ("tgt3", int(n_tgt), 3), ("src12", int(n_src), 12),
+                       ("tgt12", int(n_tgt), 12)):
+        side = getattr(rec, name)
+        bufs[name] = {"perm": np.zeros(n, np.int32), "pos": np.zeros(n, np.int32), "vec": np.zeros((n, D), np.float32),
+                      "tvec": np.zeros((n, D), np.float32), "tvec64": np.zeros((n, 3)), "tpt64": np.zeros((n, 4)),
+                      "lo": np.zeros((nodes, D), np.float32), "hi": np.zeros((nodes, D), np.float32)}
+        for key, a in bufs[name].items():
+            setattr(side, key, a.ctypes.data_as(ptr[a.dtype]))
+        side.cap = n
+        side.node_cap = nodes
+    _lib.check(L.se3icp_set_tree_record(device, C.byref(rec)), "set_tree_record")
+    out = {}
+    try:
+        yield out
+    finally:
+        L.se3icp_set_tree_record(device, None)
+    if not rec.recorded:
+        raise _lib.Se3IcpError(_lib.ERR_INTERNAL, "the call inside the block took no tree record")
+    for name in bufs:
+        side = getattr(rec, name)
+        if not side.exists:
+            out[name] = None
+            continue
+        n, nn = int(side.n), int(side.nnodes)
+        d = {key: ((a[:nn] if key in ("lo", "hi") else a[:n]) if side.written & _TREE_BITS[key] else None)
+             for key, a in bufs[name].items()}
+        d.update(n=n, D=int(side.D), L=int(side.L), nnodes=nn, G=int(side.G), H=int(side.H), role=int(side.role),
+                 written=int(side.written))
+        out[name] = d
+
+
 def register_batch_traced(pairs, method: str, params: _lib.Params | None = None, pair: int = 0,
                           max_iters: int = 160, device: int = 0):
     """register_batch with the per-iteration record of one pair (se3icp_set_trace): the

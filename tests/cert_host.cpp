@@ -187,11 +187,15 @@ typedef float (*L2Fn)(float, float, float, float, int);
 static float l2_no_thr(float d2, float, float na, float nb, int D) {
     return sqrtf(fmaxf(d2 - nncert::f32_err(d2, na, nb, D), 0.f)) * (1.f - 1e-6f);
 }
-// f32 bound of the target's own box, inflated as k_tree_leafbox does, against the f32 query
+// f32 bound of the target's own box, inflated as k_tree_leafbox does, against the f32 query.
+// The kernel's `fabsf(v) * 4.8e-7f + 1e-30f` is contracted to one v_fma_f32: fmaf here, whatever
+// this file's own contraction setting (the tree record's tests hold the kernel's boxes to this
+// form bit for bit, tests/tree_cases.py)
 static float box_lb(const float* q, const float* t, int D) {
     float s = 0.f;
     for (int r = 0; r < D; ++r) {
-        const float lo = t[r] - (fabsf(t[r]) * 4.8e-7f + 1e-30f), hi = t[r] + (fabsf(t[r]) * 4.8e-7f + 1e-30f);
+        const float infl = fmaf(fabsf(t[r]), 4.8e-7f, 1e-30f);
+        const float lo = t[r] - infl, hi = t[r] + infl;
         const float e = fmaxf(fmaxf(lo - q[r], q[r] - hi), 0.f);
         s = fmaf(e, e, s);
     }

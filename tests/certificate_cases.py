@@ -11,6 +11,8 @@ import functools
 
 import numpy as np
 
+from tree_cases import inflation_fused
+
 LD = np.longdouble
 EPS = 2.0 ** -52
 K_HIST = 256          # pose ring of the loop (csrc/common.hpp kHist)
@@ -320,7 +322,9 @@ def header_model(case, ref, defect=None):
     q64s = [r["q"].astype(np.float64) for r in ref]
     _, nb, cen = entry_norms(case, q64s[0])
     tf = (data - cen).astype(f)
-    lo, hi = tf - (np.abs(tf) * f(4.8e-7) + f(1e-30)), tf + (np.abs(tf) * f(4.8e-7) + f(1e-30))
+    # (the kernel's inflation is one fused multiply-add: tree_cases.inflation_fused, exact)
+    infl = inflation_fused(tf)
+    lo, hi = tf - infl, tf + infl
     ci, j = np.full(n, -1), np.full(n, -1)
     D1, L2 = np.zeros(n, f), np.zeros(n, f)
     tr = slice(9, 12) if D == 12 else slice(0, 3)

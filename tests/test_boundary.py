@@ -173,3 +173,67 @@ def test_setup_record_arguments_without_a_device():
     assert lib.se3icp_setup_record_version() == 1
     rc = lib.se3icp_set_setup_record(0, None)
     assert rc == (_lib.OK if se3icp.device_count() > 0 else _lib.ERR_NO_DEVICE)
+
+
+def test_tree_record_layout_matches_the_ctypes_mirror(tmp_path):
+    from se3icp import _lib
+    cc = HIPCC if os.path.exists(HIPCC) else shutil.which("hipcc")
+    if not cc:
+        pytest.skip("hipcc not available")
+    side = [f for f, _ in _lib.TreeSide._fields_]
+    rec = [f for f, _ in _lib.TreeRecord._fields_]
+    src = tmp_path / "tree_layout.cpp"
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "se3icp.h"', "int main() {",
+             '  std::printf("%zu %zu\\n", sizeof(se3icp_tree_side), sizeof(se3icp_tree_record));']
+    lines += [f'  std::printf("%zu %zu\\n", offsetof(se3icp_tree_side, {f}), sizeof(((se3icp_tree_side*)0)->{f}));'
+              for f in side]
+    lines += [f'  std::printf("%zu %zu\\n", offsetof(se3icp_tree_record, {f}), sizeof(((se3icp_tree_record*)0)->{f}));'
+              for f in rec]
+    lines += ['  std::printf("%d %d\\n", SE3ICP_TREE_PERM | SE3ICP_TREE_POS << 4 | SE3ICP_TREE_VEC << 8 | SE3ICP_TREE_TVEC << 12,'
+              ' SE3ICP_TREE_TVEC64 | SE3ICP_TREE_TPT64 << 4 | SE3ICP_TREE_BOXES << 8);',
+              '  std::printf("%d 0\\n", SE3ICP_TREE_BUILT);', "  return 0;", "}"]
+    src.write_text("\n".join(lines) + "\n")
+    exe = str(tmp_path / "tree_layout")
+    subprocess.check_call([cc, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    out = [tuple(int(x) for x in ln.split()) for ln in subprocess.run([exe], capture_output=True, text=True,
+                                                                      check=True).stdout.splitlines()]
+    assert out[0] == (C.sizeof(_lib.TreeSide), C.sizeof(_lib.TreeRecord))
+    want = [(getattr(_lib.TreeSide, f).offset, getattr(_lib.TreeSide, f).size) for f in side]
+    want += [(getattr(_lib.TreeRecord, f).offset, getattr(_lib.TreeRecord, f).size) for f in rec]
+    assert out[1:-2] == want
+    L = _lib
+    assert out[-2] == (L.TREE_PERM | L.TREE_POS << 4 | L.TREE_VEC << 8 | L.TREE_TVEC << 12,
+                       L.TREE_TVEC64 | L.TREE_TPT64 << 4 | L.TREE_BOXES << 8)
+    assert out[-1] == (L.TREE_BUILT, 0)
+    import tree_cases as T
+    assert (T.PERM, T.POS, T.VEC, T.TVEC, T.TVEC64, T.TPT64, T.BOXES, T.BUILT) == (
+        L.TREE_PERM, L.TREE_POS, L.TREE_VEC, L.TREE_TVEC, L.TREE_TVEC64, L.TREE_TPT64, L.TREE_BOXES, L.TREE_BUILT)
+
+
+def test_tree_record_arguments_without_a_device():
+    """The version entry; a bad record is SE3ICP_ERR_INVALID_ARG on any machine (the arguments are
+    checked before the device is looked up); a good one, or NULL, either arms / disarms or fails
+    loudly without a device."""
+    import se3icp
+    from se3icp import _lib
+    lib = se3icp.load()
+    assert lib.se3icp_tree_record_version() == 1
+    have = se3icp.device_count() > 0
+    assert lib.se3icp_set_tree_record(0, None) == (_lib.OK if have else _lib.ERR_NO_DEVICE)
+    for field, value in (("pair", -1), ("src3.cap", -1), ("tgt3.node_cap", -1), ("src12.cap", -5), ("tgt12.node_cap", -1)):
+        rec = _lib.TreeRecord()
+        obj = rec
+        *path, last = field.split(".")
+        for p in path:
+            obj = getattr(obj, p)
+        setattr(obj, last, value)
+        assert lib.se3icp_set_tree_record(0, C.byref(rec)) == _lib.ERR_INVALID_ARG, field
+        assert lib.se3icp_set_tree_record(77, C.byref(rec)) == _lib.ERR_INVALID_ARG, field  # (no such device either)
+    rec = _lib.TreeRecord()  # every pointer NULL, pair 0: valid
+    assert lib.se3icp_set_tree_record(0, C.byref(rec)) == (_lib.OK if have else _lib.ERR_NO_DEVICE)
+    assert lib.se3icp_set_tree_record(0, None) == (_lib.OK if have else _lib.ERR_NO_DEVICE)
+    if not have:
+        # a pair out of the call's range is that call's error; without a device the call fails first
+        with pytest.raises(_lib.Se3IcpError):
+            with se3icp.tree_record(3, 10, 10):
+                pass

@@ -158,6 +158,30 @@ hipError_t spin_phases(const volatile int32_t* slot, int n, hipStream_t s) {
     }
 }
 
+// An armed record against the call's `nslots` result slots (open_call): false if it names no slot
+// or a negative capacity; otherwise it is reset and *pair (the trace carries its own) is its slot.
+bool arm_record(se3icp_trace* tr, int64_t nslots) {
+    if (tr->pair < 0 || (int64_t)tr->pair >= nslots || tr->max_iters < 0) return false;
+    tr->iters_recorded = 0;
+    return true;
+}
+bool arm_record(se3icp_setup_record* sr, int64_t nslots, int* pair) {
+    if (sr->pair < 0 || (int64_t)sr->pair >= nslots || sr->src.cap < 0 || sr->tgt.cap < 0) return false;
+    *pair = sr->pair;
+    sr->recorded = 0;
+    sr->src.n = sr->tgt.n = 0;
+    sr->src.written = sr->tgt.written = 0;
+    return true;
+}
+bool arm_record(se3icp_tree_record* tk, int64_t nslots, int* pair) {
+    if (tk->pair < 0 || (int64_t)tk->pair >= nslots) return false;
+    for (const se3icp_tree_side* t : {&tk->src3, &tk->tgt3, &tk->src12, &tk->tgt12})
+        if (t->cap < 0 || t->node_cap < 0) return false;
+    *pair = tk->pair;
+    tk->recorded = 0;
+    return true;
+}
+
 static_assert(GS_COUNT == 9, "Engine::graph_stats_");
 constexpr size_t kShareMaxSlots = 65535;  // k_share_hash takes one grid row per slot
 constexpr int kStatSlots = 64;  // work counters: [64][kStatCols] u64 (spread against atomic contention)
@@ -439,13 +463,10 @@ int Engine::host_centroids(hipStream_t s, std::vector<double>* cen) {
     return 0;
 }
 
-int Engine::setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bool pairs, bool normalize,
-                         double scale_pre, hipStream_t s) {
-    int rc = upload_clouds(clouds, on_device, s);
-    if (rc) return rc;
+// (see engine.hpp)
+int Engine::queue_norm_params(bool pairs, bool normalize, double scale_pre, hipStream_t s) {
     const int nch = (int)h_chunks_.size();
-    View v = view();
-
+    const View v = view();
     // 1) ingest: SoA copy + sums + bbox
     launch_ingest(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
     HIPCHK(hipGetLastError());
@@ -462,21 +483,32 @@ int Engine::setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bo
         HIPCHK(hipGetLastError());
         for (int c = 0; c < nclouds_; ++c)  // (the device holds the normalization fields)
             for (int a = 0; a < 3; ++a) h_setup_[c].f32_center[a] = 0.0;
-    } else {
-        std::vector<double> cen;
-        rc = host_centroids(s, &cen);
-        if (rc) return rc;
-        for (int c = 0; c < nclouds_; ++c) {
-            // raw coordinates; f32 copies centered on the target (pairs) / own centroid (single clouds)
-            const int cc = pairs ? (c | 1) : c;
-            for (int a = 0; a < 3; ++a) {
-                h_setup_[c].norm_center[a] = 0.0;
-                h_setup_[c].f32_center[a] = cen[3 * cc + a];
-            }
-            h_setup_[c].norm_scale = 1.0;
-        }
-        HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * nclouds_, hipMemcpyHostToDevice, s));
+        return 0;
     }
+    std::vector<double> cen;
+    const int rc = host_centroids(s, &cen);
+    if (rc) return rc;
+    for (int c = 0; c < nclouds_; ++c) {
+        // raw coordinates; f32 copies centered on the target (pairs) / own centroid (single clouds)
+        const int cc = pairs ? (c | 1) : c;
+        for (int a = 0; a < 3; ++a) {
+            h_setup_[c].norm_center[a] = 0.0;
+            h_setup_[c].f32_center[a] = cen[3 * cc + a];
+        }
+        h_setup_[c].norm_scale = 1.0;
+    }
+    HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * nclouds_, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+int Engine::setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bool pairs, bool normalize,
+                         double scale_pre, hipStream_t s) {
+    int rc = upload_clouds(clouds, on_device, s);
+    if (rc) return rc;
+    rc = queue_norm_params(pairs, normalize, scale_pre, s);
+    if (rc) return rc;
+    const int nch = (int)h_chunks_.size();
+    View v = view();
 
     // 3) normalize in place + f32 copy
     launch_normalize(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
@@ -493,13 +525,13 @@ int Engine::setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bo
 
 // kNN / TOLDI frames / normals of the clouds that were normalized and given their 3-D trees
 // (step 4 of setup_clouds; Engine::register_graph runs it over its classes).
-int Engine::setup_knn(hipStream_t s) {
+int Engine::setup_knn(hipStream_t s, const SelectPlan* sel) {
     const View v = view();
     bool any_knn = false;
     for (int c = 0; c < nclouds_; ++c) any_knn |= h_setup_[c].k_knn > 0;
     if (any_knn) {
         HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
-        HIPCHK(hipEventRecord(ev_[6], s));
+        HIPCHK(hipEventRecord(ev_[EV_LRF_BEGIN], s));
         // neighbourhoods over kSmallK (Kw = min(k, n)) go to k_knn_big, the rest to the LDS
         // kernels; the global-buffer kernel's candidate buffers are sized to the largest
         int kw_big = 0, n_big = 0;
@@ -529,27 +561,12 @@ int Engine::setup_knn(hipStream_t s) {
             big(nullptr, nullptr, kSmallK);
         } else {
             // eight queries per wavefront; the few it cannot resolve from f32 keys (and every
-            // query of a cloud whose k it cannot hold) go to the exact kernels
-            // waves aligned to each cloud's first point (results independent of the batch)
-            // Two wave tables: the seeded clouds of select_by_class (graph.hpp, graph_plan_seeds)
-            // run in a launch of their own behind the one that stores their seeds.
-            // The taking clouds among them (graph_plan_takes) have a third table: a launch that
-            // takes the lists the first one stored, then a seeded launch over the same table for
-            // the waves that could not (sources, take, redo in stream order).
-            const bool seeding = seed_on_, taking = seed_on_ && take_on_;
+            // query of a cloud whose k it cannot hold) go to the exact kernels.  Three wave tables
+            // (graph.hpp, select_wave_tables): sources, take, redo in stream order.
+            const bool seeding = sel && sel->seeds, taking = seeding && sel->takes;
             const int nt = nclouds_ + 1;
-            std::vector<int32_t> wb(3 * (size_t)nt, 0);
-            // (a cloud that wants no neighbours gets no waves: the kernel's search for a wave's
-            // cloud takes the last one that starts at or before it)
-            for (int c = 0; c < nclouds_; ++c) {
-                const int waves = h_setup_[c].k_knn > 0 ? (h_clouds_[c].n + 7) / 8 : 0;
-                const bool sd = seeding && seed_ref_[c].load >= 0;
-                const bool tk = sd && taking && (take_flag_[c] & 2);
-                wb[c + 1] = wb[c] + (sd ? 0 : waves);
-                wb[nt + c + 1] = wb[nt + c] + (sd && !tk ? waves : 0);
-                wb[2 * nt + c + 1] = wb[2 * nt + c] + (tk ? waves : 0);
-            }
-            const int nw = wb[nclouds_], nw_sd = wb[nt + nclouds_], nw_tk = wb[2 * nt + nclouds_];
+            const WaveTables wt = select_wave_tables(nclouds_, h_clouds_.data(), h_setup_.data(), sel);
+            const int nw = wt.nw, nw_sd = wt.nw_sd, nw_tk = wt.nw_tk;
             if (!ensure<int32_t>(d_lrf_fb_, (size_t)8 * ((size_t)nw + nw_sd + nw_tk) + 64) ||
                 !ensure<int32_t>(d_lrf_fbn_, 2 + 3 * (size_t)nt))
                 return SE3ICP_ERR_OUT_OF_MEMORY;
@@ -557,32 +574,32 @@ int Engine::setup_knn(hipStream_t s) {
             int32_t* fb = (int32_t*)d_lrf_fb_.p;
             int32_t* fbn = (int32_t*)d_lrf_fbn_.p;
             HIPCHK(hipMemsetAsync(fbn, 0, 2 * sizeof(int32_t), s));
-            HIPCHK(hipMemcpyAsync(d_wb, wb.data(), sizeof(int32_t) * 3 * nt, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_wb, wt.wb.data(), sizeof(int32_t) * 3 * nt, hipMemcpyHostToDevice, s));
             if (seeding) {
                 // (with taking the bounds Lb follow the seeds: one fill marks both absent)
-                const size_t nseed = (size_t)seed_floats_ * (taking ? 2 : 1);
+                const size_t nseed = (size_t)sel->seed_floats * (taking ? 2 : 1);
                 if (!ensure<float>(d_seed_, nseed) || !ensure<SeedRef>(d_seed_ref_, nclouds_))
                     return SE3ICP_ERR_OUT_OF_MEMORY;
                 HIPCHK(hipMemsetAsync(d_seed_.p, 0xff, sizeof(float) * nseed, s));  // all ones: absent
-                HIPCHK(hipMemcpyAsync(d_seed_ref_.p, seed_ref_.data(), sizeof(SeedRef) * nclouds_, hipMemcpyHostToDevice, s));
+                HIPCHK(hipMemcpyAsync(d_seed_ref_.p, sel->seed_ref.data(), sizeof(SeedRef) * nclouds_, hipMemcpyHostToDevice, s));
                 const SeedRef* sref = (const SeedRef*)d_seed_ref_.p;
                 float* sbuf = (float*)d_seed_.p;
                 TakeArgs tk{nullptr, nullptr, nullptr, 0, 0, 0};
                 if (taking && nw_tk > 0) {
-                    if (!ensure<uint32_t>(d_take_lists_, (size_t)seed_floats_ * (size_t)take_stride_) ||
+                    if (!ensure<uint32_t>(d_take_lists_, (size_t)sel->seed_floats * (size_t)sel->take_stride) ||
                         !ensure<int32_t>(d_take_flag_, nclouds_) || !ensure<unsigned char>(d_take_mask_, (size_t)nw_tk + 64))
                         return SE3ICP_ERR_OUT_OF_MEMORY;
-                    HIPCHK(hipMemcpyAsync(d_take_flag_.p, take_flag_.data(), sizeof(int32_t) * nclouds_, hipMemcpyHostToDevice, s));
+                    HIPCHK(hipMemcpyAsync(d_take_flag_.p, sel->take_flag.data(), sizeof(int32_t) * nclouds_, hipMemcpyHostToDevice, s));
                     HIPCHK(hipMemsetAsync(d_take_mask_.p, 0, (size_t)nw_tk + 64, s));
-                    tk = TakeArgs{(const int32_t*)d_take_flag_.p, (uint32_t*)d_take_lists_.p, nullptr, take_stride_,
-                                  (int32_t)seed_floats_, lrf_taking_};
+                    tk = TakeArgs{(const int32_t*)d_take_flag_.p, (uint32_t*)d_take_lists_.p, nullptr, sel->take_stride,
+                                  (int32_t)sel->seed_floats, sel->take_mode};
                 }
-                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s, sref, sbuf, false, lrf_seeding_, &tk);
-                launch_lrf8(v, d_wb + nt, 0, nw_sd, fb, fbn, s, sref, sbuf, true, lrf_seeding_);
+                launch_lrf8(v, d_wb, 0, nw, fb, fbn, s, sref, sbuf, false, sel->seed_mode, &tk);
+                launch_lrf8(v, d_wb + nt, 0, nw_sd, fb, fbn, s, sref, sbuf, true, sel->seed_mode);
                 if (tk.flag != nullptr) {
                     tk.mask = (unsigned char*)d_take_mask_.p;
-                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, lrf_seeding_, &tk, true);
-                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, lrf_seeding_, &tk);
+                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, sel->seed_mode, &tk, true);
+                    launch_lrf8(v, d_wb + 2 * nt, 0, nw_tk, fb, fbn, s, sref, sbuf, true, sel->seed_mode, &tk);
                 }
             } else {
                 launch_lrf8(v, d_wb, 0, nw, fb, fbn, s);
@@ -590,7 +607,7 @@ int Engine::setup_knn(hipStream_t s) {
             launch_lrf_list(v, fb, fbn, s);
             big(fb, fbn, kSmallK);
         }
-        HIPCHK(hipEventRecord(ev_[7], s));
+        HIPCHK(hipEventRecord(ev_[EV_LRF_END], s));
         HIPCHK(hipGetLastError());
         // work counters: copied now, read at the next synchronisation (read_lrf_stats)
         if (h_lrf_stats_.reserve((size_t)kStatCols * kStatSlots)) return SE3ICP_ERR_OUT_OF_MEMORY;
@@ -609,7 +626,7 @@ int Engine::read_lrf_stats() {
     for (int i = 0; i < kStatSlots; ++i)
         for (int k = 0; k < kStatCols; ++k) sum[k] += (double)h_lrf_stats_[kStatCols * i + k];
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev_[6], ev_[7]));
+    HIPCHK(hipEventElapsedTime(&ms, ev_[EV_LRF_BEGIN], ev_[EV_LRF_END]));
     ktimes_.lrf_ms = ms;
     ktimes_.lrf_queries = sum[0];
     ktimes_.lrf_leaves = sum[1];
@@ -653,8 +670,8 @@ int Engine::read_lrf_stats() {
 
 // Wait for everything queued on `s` (polling, see spin_wait).
 int Engine::sync_stream(hipStream_t s) {
-    HIPCHK(hipEventRecord(ev_[15], s));
-    HIPCHK(spin_wait(ev_[15]));
+    HIPCHK(hipEventRecord(ev_[EV_SYNC], s));
+    HIPCHK(spin_wait(ev_[EV_SYNC]));
     return read_lrf_stats();
 }
 
@@ -678,33 +695,16 @@ int Engine::setup_chunks(int npairs, hipStream_t s) {
 // The opening of a registration call (see engine.hpp).
 int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    se3icp_trace* tr = c->tr = trace_;  // one-shot: the record covers this call only
-    trace_ = nullptr;
-    se3icp_setup_record* sr = c->sr = setup_rec_;  // one-shot likewise
-    setup_rec_ = nullptr;
-    se3icp_tree_record* tk = c->tr_rec = tree_rec_;  // and the tree record
-    tree_rec_ = nullptr;
+    c->tr = std::exchange(trace_, nullptr);  // one-shot: the records cover this call only, rejected or not
+    c->sr = std::exchange(setup_rec_, nullptr);
+    c->tk = std::exchange(tree_rec_, nullptr);
     for (std::vector<TreeLog>& log : tree_log_) log.clear();
     pose_raw_.clear();  // (a call without a posed edge plans its seeds over clouds)
     pose_rigid_.clear();
     if (args) return args;
-    if (tr && (tr->pair < 0 || (int64_t)tr->pair >= nslots || tr->max_iters < 0)) return SE3ICP_ERR_INVALID_ARG;
-    if (tr) tr->iters_recorded = 0;
-    if (sr && (sr->pair < 0 || (int64_t)sr->pair >= nslots || sr->src.cap < 0 || sr->tgt.cap < 0))
-        return SE3ICP_ERR_INVALID_ARG;
-    if (sr) {
-        c->sr_pair = sr->pair;
-        sr->recorded = 0;
-        sr->src.n = sr->tgt.n = 0;
-        sr->src.written = sr->tgt.written = 0;
-    }
-    if (tk) {
-        if (tk->pair < 0 || (int64_t)tk->pair >= nslots) return SE3ICP_ERR_INVALID_ARG;
-        for (const se3icp_tree_side* t : {&tk->src3, &tk->tgt3, &tk->src12, &tk->tgt12})
-            if (t->cap < 0 || t->node_cap < 0) return SE3ICP_ERR_INVALID_ARG;
-        c->tr_pair = tk->pair;
-        tk->recorded = 0;
-    }
+    if (c->tr && !arm_record(c->tr, nslots)) return SE3ICP_ERR_INVALID_ARG;
+    if (c->sr && !arm_record(c->sr, nslots, &c->sr_pair)) return SE3ICP_ERR_INVALID_ARG;
+    if (c->tk && !arm_record(c->tk, nslots, &c->tk_pair)) return SE3ICP_ERR_INVALID_ARG;
     if (rest) return rest;
     HIPCHK(hipSetDevice(dev_));
     c->s = user_stream ? user_stream : stream_;
@@ -713,9 +713,9 @@ int Engine::open_call(int args, int64_t nslots, int rest, hipStream_t user_strea
     for (int64_t& x : take_stats_) x = 0;
     for (int64_t& x : tree_stats_) x = 0;
     tree_donor_.clear();
-    // phase times on the GPU timeline (the host does not wait for the setup): events
-    // 12 (begin), 13 (setup done), 14 (loop done)
-    HIPCHK(hipEventRecord(ev_[12], c->s));
+    // phase times on the GPU timeline (the host does not wait for the setup): call begin,
+    // setup done, loop done
+    HIPCHK(hipEventRecord(ev_[EV_CALL_BEGIN], c->s));
     return 0;
 }
 
@@ -739,7 +739,7 @@ int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const
     HIPCHK(hipMemsetAsync(d_corr_idx_.p, 0xff, sizeof(int32_t) * ld_, s));  // no previous match yet
     HIPCHK(hipMemsetAsync(d_stats_.p, 0, sizeof(unsigned long long) * kStatCols * kStatSlots, s));
     for (double& t : trace_prev_) t = 0;
-    HIPCHK(hipEventRecord(ev_[13], s));
+    HIPCHK(hipEventRecord(ev_[EV_SETUP_DONE], s));
     // The armed setup record, taken here: every entry's setup is complete (the kNN / frame /
     // normal kernels, k_graph_share's copies, k_sweep_expand's weighted rows) and nothing of the
     // loop is queued.  What ran between the end of the setup and this point -- the 12-D trees,
@@ -747,20 +747,29 @@ int Engine::run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const
     // trees' own buffers, the work tables, cert, gcost, cls, corr_idx and stats: none of them
     // writes xyz64, fr64, nrm64, conf64 or the setup table, and the loop only reads them, so
     // these are the arrays the loop consumes.  Unarmed, nothing is queued here.
-    if (c.sr) {
-        rc = record_setup(c.sr, c.sr_pair, s);
-        if (rc) return rc;
-    }
+    if (c.sr && (rc = record_setup(c.sr, c.sr_pair, s))) return rc;
     // The armed tree record, at the same point: both trees of the pair's slots are complete
     // (the 3-D ones of the setup, a sweep's replicas, the 12-D ones above) and the loop only
     // reads them.
-    if (c.tr_rec) {
-        rc = record_trees(c.tr_rec, c.tr_pair, s);
-        if (rc) return rc;
-    }
+    if (c.tk && (rc = record_trees(c.tk, c.tk_pair, s))) return rc;
     const ReportReq rq{ropts, reports};
     return run_loop(npairs, ns, mp.kind, mp.est, vprm, pairs_per_variant, sweep, c.tr, out, s,
                     (ropts && reports) ? &rq : nullptr);
+}
+
+// The Call of a sweep group (engine.hpp).
+Engine::Call Engine::group_call(const Call& c, int v0, int g, int P, se3icp_trace* gtr) {
+    auto local = [&](int pair) { return (pair >= v0 * P && pair < (v0 + g) * P) ? pair - v0 * P : -1; };
+    Call gc;
+    gc.s = c.s;
+    if (c.tr && local(c.tr->pair) >= 0) {
+        *gtr = *c.tr;
+        gtr->pair = local(c.tr->pair);
+        gc.tr = gtr;
+    }
+    if (c.sr && (gc.sr_pair = local(c.sr_pair)) >= 0) gc.sr = c.sr;
+    if (c.tk && (gc.tk_pair = local(c.tk_pair)) >= 0) gc.tk = c.tk;
+    return gc;
 }
 
 int Engine::register_batch(int npairs, const double* const* src, const int64_t* ns, const double* const* tgt,
@@ -804,11 +813,10 @@ int Engine::register_batch(int npairs, const double* const* src, const int64_t* 
 
 // ----------------------------------------------------------------------------- shared slots of a device batch
 // setup_clouds(clouds, on_device, pairs, normalize) for slots that may hold one cloud several
-// times (engine.hpp).  Every kernel setup_clouds queues is queued here, in its order and on its
-// tables, so a call without a confirmed duplicate is that path plus k_share_hash.  With tree
-// sharing off the host waits for the hashes while the device normalizes and builds the 3-D
-// trees; with it (the default) the trees are queued in two parts around the compare flags, see
-// below.
+// times (engine.hpp), through the same queue_norm_params: a call without a confirmed duplicate is
+// that path plus k_share_hash.  With tree sharing off the host waits for the hashes while the
+// device normalizes and builds the 3-D trees; with it (the default) the trees are queued in two
+// parts around the compare flags, see below.
 int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const MethodPlan& mp, double scale_pre,
                                hipStream_t s) {
     const int U = (int)clouds.size();
@@ -824,34 +832,13 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
     HIPCHK(hipMemsetAsync(d_share_hash_.p, 0, sizeof(uint64_t) * U, s));
     launch_share_hash(v, (unsigned long long*)d_share_hash_.p, s);
     HIPCHK(hipMemcpyAsync(h_share_hash_, d_share_hash_.p, sizeof(uint64_t) * U, hipMemcpyDeviceToHost, s));
-    launch_ingest(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
-    HIPCHK(hipGetLastError());
+    // (the host-centroid wait of a vanilla method brings the hashes with it)
+    rc = queue_norm_params(true, se3, scale_pre, s);
+    if (rc) return rc;
     if (se3) {
-        // (the device forms the normalization parameters, as in setup_clouds; its table comes
-        // back with the hashes: a class is the bits the device normalizes a slot with)
-        if (!ensure<double>(d_scales_, std::max(1, nclouds_ / 2))) return SE3ICP_ERR_OUT_OF_MEMORY;
-        launch_pair_centers(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_partial_.p, (double*)d_centers_.p,
-                            s);
-        launch_radius(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_centers_.p, (double*)d_partial_.p, s);
-        launch_pair_scales(v, (const ChunkWork*)d_chunks_.p, nch, (const double*)d_partial_.p,
-                           (const double*)d_centers_.p, scale_pre, (double*)d_scales_.p, s);
-        HIPCHK(hipGetLastError());
+        // (its table comes back with the hashes: a class is the bits the device normalizes a slot with)
         HIPCHK(hipMemcpyAsync(h_share_setup_, d_setup_.p, sizeof(CloudSetup) * U, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ev_[10], s));
-        for (int c = 0; c < nclouds_; ++c)
-            for (int a = 0; a < 3; ++a) h_setup_[c].f32_center[a] = 0.0;
-    } else {
-        std::vector<double> cen;
-        rc = host_centroids(s, &cen);  // (the hashes arrive with this wait)
-        if (rc) return rc;
-        for (int c = 0; c < nclouds_; ++c) {
-            for (int a = 0; a < 3; ++a) {
-                h_setup_[c].norm_center[a] = 0.0;
-                h_setup_[c].f32_center[a] = cen[3 * (c | 1) + a];
-            }
-            h_setup_[c].norm_scale = 1.0;
-        }
-        HIPCHK(hipMemcpyAsync(d_setup_.p, h_setup_.data(), sizeof(CloudSetup) * nclouds_, hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev_[EV_SHARE_HASH], s));
     }
     launch_normalize(v, (const ChunkWork*)d_chunks_.p, nch, (double*)d_partial_.p, s);
     HIPCHK(hipGetLastError());
@@ -865,7 +852,7 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
         rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p);
         if (rc) return rc;
     }
-    if (se3) HIPCHK(spin_wait(ev_[10]));
+    if (se3) HIPCHK(spin_wait(ev_[EV_SHARE_HASH]));
 
     // ---- candidates by (n, hash), confirmed byte for byte
     std::vector<int64_t> n(U);
@@ -882,14 +869,14 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
         launch_share_compare(v, (const SharePair*)d_share_pairs_.p, ncand, (int32_t*)d_share_same_.p, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_share_same_, d_share_same_.p, sizeof(int32_t) * U, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipEventRecord(ev_[11], s));
+        HIPCHK(hipEventRecord(ev_[EV_SHARE_FLAGS], s));
         std::vector<int32_t> role(U);
         if (adopt) {
             for (int u = 0; u < U; ++u) role[u] = first[u] == u ? kTreeBuilds : kTreeAbsent;
             rc = build_tree(3, (const float*)d_xyz32_.p, s, (const double*)d_xyz64_.p, &role, &tree_tab_a_);
             if (rc) return rc;
         }
-        HIPCHK(spin_wait(ev_[11]));
+        HIPCHK(spin_wait(ev_[EV_SHARE_FLAGS]));
         nc = share_clouds(U, first.data(), h_share_same_, &cloud);
         if (adopt) {
             // a confirmed slot adopts; a hash-equal slot the compare rejected builds
@@ -908,10 +895,10 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
 
     // ---- classes: a cloud under the bits the device normalizes the slot with
     const CloudSetup* dev_table = se3 ? (const CloudSetup*)h_share_setup_ : h_setup_.data();
-    share_setup_.assign(dev_table, dev_table + U);
+    const std::vector<CloudSetup> table(dev_table, dev_table + U);
     std::vector<GraphUse> use(U);
     for (int u = 0; u < U; ++u) {
-        const CloudSetup& st = share_setup_[u];
+        const CloudSetup& st = table[u];
         use[u].cloud = cloud[u];
         use[u].k_nrm = st.k_nrm;
         use[u].norm_scale = st.norm_scale;
@@ -924,117 +911,36 @@ int Engine::setup_pairs_shared(const std::vector<CloudReq>& clouds, const Method
     graph_plan_uses(U, use.data(), se3, true, &plan);
     graph_stats_[GS_CLOUDS] = nc;
     graph_stats_[GS_CLASSES] = (int64_t)plan.classes.size();
-    return select_by_class(plan, share_setup_, mp, s);
+    return select_by_class(plan, table, mp, s);
 }
 
-// The neighbour selection of planned uses (engine.hpp).  The tables the copies below read stay
-// alive in the engine until the call's last synchronisation.
+// The neighbour selection of planned uses (engine.hpp): plan it (graph.hpp), copy the tables,
+// select, then restore the batch's table and hand the homes' results to the other uses.
 int Engine::select_by_class(const GraphPlan& plan, const std::vector<CloudSetup>& batch, const MethodPlan& mp,
                             hipStream_t s) {
-    const int U = (int)batch.size(), K = (int)plan.classes.size();
-    const bool se3 = mp.se3;
-    std::vector<int32_t> home(K, -1);  // first use of each class
-    for (int u = 0; u < U; ++u)
-        if (home[plan.use_class[u]] < 0) home[plan.use_class[u]] = u;
-    sel_batch_ = batch;
-    sel_run_ = sel_batch_;
-    sel_chunks_.clear();
-    sel_seg_.assign(U, GraphSeg{});
-    graph_stats_[GS_FULL] = 0;
-    for (int u = 0; u < U; ++u) {
-        const int k = plan.use_class[u];
-        const GraphClass& gc = plan.classes[k];
-        // the setup's table: a home use selects for its class (the largest normals k of the
-        // class's uses; none where another class of the cloud owns the normals), the others
-        // select nothing
-        CloudSetup& st = sel_run_[u];
-        const bool is_home = home[k] == u;
-        st.k_lrf = is_home ? mp.k_lrf : 0;
-        st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
-        st.k_knn = std::max(st.k_lrf, st.k_nrm);
-        graph_stats_[GS_FULL] += st.k_knn > 0;
-        const int hf = home[k], hn = home[gc.nrm_from];  // where its frames / normals are computed
-        sel_seg_[u] = GraphSeg{h_clouds_[hf].off, hf, h_clouds_[hn].off, (hf != u && se3) ? 1 : 0};
-        if ((hf != u && se3) || hn != u)
-            for (int64_t p0 = 0; p0 < h_clouds_[u].n; p0 += kChunk) sel_chunks_.push_back(ChunkWork{u, (int32_t)p0});
+    const int U = (int)batch.size();
+    sel_ = graph_plan_selection(plan, h_clouds_.data(), batch.data(), mp.k_lrf,
+                                SelectSwitches{lrf_seeding_, lrf_taking_, lrf_exact_only_, knn_list_, pose_seeding_},
+                                tree_donor_, pose_raw_, pose_rigid_);
+    graph_stats_[GS_FULL] = sel_.full;
+    if (sel_.seeds) {
+        seed_stats_[0] = sel_.seeded;
+        init_stats_[IS_CROSS_SEEDED] = sel_.cross;
     }
-    const int nchS = (int)sel_chunks_.size();
+    if (sel_.takes) take_stats_[TS_CLASSES] = sel_.taking;
+    const int nchS = (int)sel_.chunks.size();
     if (!ensure<ChunkWork>(g_chunks_, nchS) || !ensure<GraphSeg>(g_seg_, U)) return SE3ICP_ERR_OUT_OF_MEMORY;
-    // seeding: a cloud's later classes start from its first class's neighbour distances
-    // (graph_plan_seeds; k_lrf8 only, so not under se3icp_set_lrf_exact)
-    seed_ref_.clear();
-    seed_floats_ = 0;
-    if (lrf_seeding_ != 1 && lrf_exact_only_ == 0 && !knn_list_) {
-        std::vector<int32_t> kk(K);
-        std::vector<int64_t> nn(K);
-        for (int k = 0; k < K; ++k) {
-            kk[k] = sel_run_[home[k]].k_knn;
-            nn[k] = h_clouds_[home[k]].n;
-        }
-        std::vector<SeedClass> sc;
-        int32_t cross = 0;
-        const int seeded = pose_raw_.empty()
-                               ? graph_plan_seeds(plan, kk.data(), nn.data(), &sc)
-                               : graph_plan_seeds_posed(plan, kk.data(), nn.data(), pose_raw_.data(), pose_rigid_.data(),
-                                                        pose_seeding_ == 0, &sc, &cross);
-        int64_t total = 0;
-        for (int k = 0; k < K; ++k)
-            if (sc[k].from >= 0) total += nn[k];  // (an upper bound of the buffer: a source may seed several)
-        if (seeded > 0 && total <= INT32_MAX) {
-            seed_ref_.assign(U, SeedRef{-1, -1, 1.0});
-            for (int k = 0; k < K; ++k) {
-                if (sc[k].from < 0) continue;
-                SeedRef& src = seed_ref_[home[sc[k].from]];
-                if (src.store < 0) {
-                    src.store = (int32_t)seed_floats_;
-                    seed_floats_ += nn[k];
-                }
-                seed_ref_[home[k]].load = src.store;
-                seed_ref_[home[k]].rho2 = sc[k].rho2;
-            }
-            seed_stats_[0] = seeded;
-            init_stats_[IS_CROSS_SEEDED] = cross;
-            seed_on_ = true;
-            // taking: a seeded class with its source's tree order takes the source's lists
-            // (graph_plan_takes); only with both switches at their defaults (taking mode 2 is
-            // the default with every bound halved)
-            take_flag_.clear();
-            take_stride_ = 0;
-            if (lrf_seeding_ == 0 && lrf_taking_ != 1 && (int)tree_donor_.size() == U) {
-                std::vector<uint8_t> tk;
-                const int taking = graph_plan_takes(plan, sc, kk.data(), nn.data(), home.data(), tree_donor_, &tk);
-                int64_t kw_max = 0;
-                for (int k = 0; k < K; ++k)
-                    if (tk[k]) kw_max = std::max<int64_t>(kw_max, std::min<int64_t>(kk[k], nn[k]));
-                // (lists of Kw <= 128 entries, 16-B aligned; longer ones are never taken)
-                const int64_t stride = (std::min<int64_t>(kw_max, kSmallK) + 3) & ~(int64_t)3;
-                if (taking > 0 && 2 * seed_floats_ <= INT32_MAX) {
-                    take_flag_.assign(U, 0);
-                    for (int k = 0; k < K; ++k) {
-                        if (!tk[k]) continue;
-                        take_flag_[home[k]] |= 2;
-                        take_flag_[home[sc[k].from]] |= 1;
-                    }
-                    take_stride_ = (int)stride;
-                    take_stats_[TS_CLASSES] = taking;
-                    take_on_ = true;
-                }
-            }
-        }
-    }
-    h_setup_ = sel_run_;
-    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_run_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
-    const int rc = setup_knn(s);
-    seed_on_ = false;  // (seed_ref_ itself stays: the copy that reads it may still be queued)
-    take_on_ = false;  // (as does take_flag_)
+    h_setup_ = sel_.run;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_.run.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
+    const int rc = setup_knn(s, &sel_);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
     // the batch's own table from here on (the copies below read cf_target of the use itself)
-    h_setup_ = sel_batch_;
-    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_batch_.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
+    h_setup_ = sel_.batch;
+    HIPCHK(hipMemcpyAsync(d_setup_.p, sel_.batch.data(), sizeof(CloudSetup) * U, hipMemcpyHostToDevice, s));
     if (nchS > 0) {
-        HIPCHK(hipMemcpyAsync(g_chunks_.p, sel_chunks_.data(), sizeof(ChunkWork) * nchS, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(g_seg_.p, sel_seg_.data(), sizeof(GraphSeg) * U, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g_chunks_.p, sel_.chunks.data(), sizeof(ChunkWork) * nchS, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(g_seg_.p, sel_.seg.data(), sizeof(GraphSeg) * U, hipMemcpyHostToDevice, s));
         launch_graph_share(view(), (const ChunkWork*)g_chunks_.p, nchS, (const GraphSeg*)g_seg_.p, s);
         HIPCHK(hipGetLastError());
     }
@@ -1214,8 +1120,8 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
         if (loop_detail_[it % kLoopRing]) HIPCHK(spin_wait(ev[6]));
         if (last && lag == 1) {
             if (!loop_detail_[it % kLoopRing]) {
-                HIPCHK(hipEventRecord(ev_[15], s));
-                HIPCHK(spin_wait(ev_[15]));
+                HIPCHK(hipEventRecord(ev_[EV_SYNC], s));
+                HIPCHK(spin_wait(ev_[EV_SYNC]));
             }
         } else {
             HIPCHK(spin_phases(h_phase_ + (size_t)(it % kLoopRing) * npairs, npairs, s));
@@ -1306,7 +1212,7 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
             break;
         }
     }
-    HIPCHK(hipEventRecord(ev_[14], s));
+    HIPCHK(hipEventRecord(ev_[EV_LOOP_DONE], s));
     HIPCHK(hipMemcpyAsync(h_state_, d_state_.p, sizeof(PairState) * npairs, hipMemcpyDeviceToHost, s));
     // the device's GetCenter results, for the de-normalization (h_partial_ holds >= 9 * nclouds);
     // replicas of a sweep group share their base clouds' centers
@@ -1357,15 +1263,15 @@ int Engine::run_loop(int npairs, const int64_t* ns, int kind, int est, const se3
     float setup_ms = 0, loop_ms = 0;
     if (sweep) {
         float shared_ms = 0, group_ms = 0;
-        HIPCHK(hipEventElapsedTime(&shared_ms, ev_[12], ev_[8]));
-        HIPCHK(hipEventElapsedTime(&group_ms, ev_[9], ev_[13]));
+        HIPCHK(hipEventElapsedTime(&shared_ms, ev_[EV_CALL_BEGIN], ev_[EV_SHARED_DONE]));
+        HIPCHK(hipEventElapsedTime(&group_ms, ev_[EV_GROUP_BEGIN], ev_[EV_SETUP_DONE]));
         setup_ms = shared_ms + group_ms;
         ktimes_.setup_ms = shared_ms;
     } else {
-        HIPCHK(hipEventElapsedTime(&setup_ms, ev_[12], ev_[13]));
+        HIPCHK(hipEventElapsedTime(&setup_ms, ev_[EV_CALL_BEGIN], ev_[EV_SETUP_DONE]));
         ktimes_.setup_ms = setup_ms;
     }
-    HIPCHK(hipEventElapsedTime(&loop_ms, ev_[13], ev_[14]));
+    HIPCHK(hipEventElapsedTime(&loop_ms, ev_[EV_SETUP_DONE], ev_[EV_LOOP_DONE]));
 
     int worst = 0;
     for (int p = 0; p < npairs; ++p) {
@@ -1494,7 +1400,6 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     Call call;
     int rc = open_call(args, (int64_t)nvariants * P, rest, user_stream, &call);
     if (rc) return rc;
-    se3icp_trace* const tr = call.tr;
     hipStream_t s = call.s;
     const bool se3 = mp.se3;
     const se3icp_params& prm0 = variants[0];
@@ -1540,7 +1445,7 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     if (rc) return rc;
     if (se3)
         HIPCHK(hipMemcpyAsync(d_raw_.p, d_fr64_.p, sizeof(double) * 12 * (size_t)N, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipEventRecord(ev_[8], s));
+    HIPCHK(hipEventRecord(ev_[EV_SHARED_DONE], s));
     const std::vector<CloudDev> base_clouds = h_clouds_;
     const std::vector<CloudSetup> base_setup = h_setup_;
 
@@ -1554,7 +1459,7 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
     for (int gi = 0; gi < ngroups; ++gi) {
         int v0 = 0, g = 0;
         sweep_group(nvariants, G, gi, &v0, &g);
-        HIPCHK(hipEventRecord(ev_[9], s));
+        HIPCHK(hipEventRecord(ev_[EV_GROUP_BEGIN], s));
         // ---- the group's batch: g * P virtual pairs over g * 2P virtual clouds
         nclouds_ = g * nbase;
         npairs_ = g * P;
@@ -1594,30 +1499,17 @@ int Engine::register_sweep(int P, const double* const* src, const int64_t* ns, c
         a.hi3 = (float*)t3_.hi.p;
         launch_sweep_expand(view(), a, s);
         HIPCHK(hipGetLastError());
-        // the armed trace, if its pair is in this group (result index v * P + p)
+        // the armed records whose pair is in this group; the tree record's replicas: their 3-D
+        // trees are copies of their base clouds'
         se3icp_trace gtr{};
-        se3icp_trace* use = nullptr;
-        if (tr && tr->pair >= v0 * P && tr->pair < (v0 + g) * P) {
-            gtr = *tr;
-            gtr.pair = tr->pair - v0 * P;
-            use = &gtr;
-        }
-        // the armed setup record likewise: the group's replica of the pair, after its expansion
-        Call gcall{use, s};
-        if (call.sr && call.sr_pair >= v0 * P && call.sr_pair < (v0 + g) * P) {
-            gcall.sr = call.sr;
-            gcall.sr_pair = call.sr_pair - v0 * P;
-        }
-        // and the armed tree record: the replicas' 3-D trees are copies of their base clouds'
-        if (call.tr_rec && call.tr_pair >= v0 * P && call.tr_pair < (v0 + g) * P) {
-            gcall.tr_rec = call.tr_rec;
-            gcall.tr_pair = call.tr_pair - v0 * P;
+        const Call gcall = group_call(call, v0, g, P, &gtr);
+        if (gcall.tk) {
             tree_log_[0].resize(nclouds_);
             for (int c = nbase; c < nclouds_; ++c) tree_log_[0][c] = tree_log_[0][c % nbase];
         }
         rc = run_pairs(mp, g * P, vns.data(), vnt.data(), variants + v0, P, true, gcall, out + (size_t)v0 * P,
                        ropts, reports ? reports + (size_t)v0 * P : nullptr);
-        if (use) tr->iters_recorded = gtr.iters_recorded;
+        if (gcall.tr) call.tr->iters_recorded = gtr.iters_recorded;
         if (rc && rc != SE3ICP_ERR_NONFINITE) return rc;
         if (rc) worst = rc;
     }
@@ -2092,20 +1984,29 @@ int Engine::record_trees(se3icp_tree_record* rec, int pair, hipStream_t s) {
 }
 
 // ----------------------------------------------------------------------------- stage entry points
-int Engine::knn_self(const double* xyz, int64_t n, int k, int32_t* idx) {
+// The front of knn_self, toldi_frames and estimate_normals: the argument checks, then the setup of
+// one cloud that stands alone with k neighbours, frames (k_lrf) or normals (k_nrm) of them.
+int Engine::setup_single(const double* xyz, const void* out, int64_t n, int k, bool frames, bool normals) {
     if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    if (!xyz || !idx || n <= 0) return n <= 0 ? SE3ICP_ERR_EMPTY_CLOUD : SE3ICP_ERR_INVALID_ARG;
+    if (!xyz || !out || n <= 0) return n <= 0 ? SE3ICP_ERR_EMPTY_CLOUD : SE3ICP_ERR_INVALID_ARG;
     if (k <= 0) return SE3ICP_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(dev_));
     npairs_ = 0;
-    int rc = alloc_points(n, k, true);
+    const int rc = alloc_points(n, k, !frames && !normals);  // (the sorted lists: knn_self)
     if (rc) return rc;
     std::vector<CloudReq> cl(1);
     cl[0].in = xyz;
     cl[0].n = n;
     cl[0].st.k_knn = k;
+    cl[0].st.k_lrf = frames ? k : 0;
+    cl[0].st.k_nrm = normals ? k : 0;
+    cl[0].st.alpha = cl[0].st.beta = frames ? 1.0 : 0.0;
     cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
+    return setup_clouds(cl, false, false, false, 1.0, stream_);
+}
+
+int Engine::knn_self(const double* xyz, int64_t n, int k, int32_t* idx) {
+    const int rc = setup_single(xyz, idx, n, k, false, false);
     if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(idx, sizeof(int32_t) * k, d_knn_.p, sizeof(int32_t) * kmax_, sizeof(int32_t) * k, n,
                             hipMemcpyDeviceToHost, stream_));
@@ -2114,22 +2015,7 @@ int Engine::knn_self(const double* xyz, int64_t n, int k, int32_t* idx) {
 }
 
 int Engine::toldi_frames(const double* xyz, int64_t n, int k, double* frames) {
-    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    if (!xyz || !frames || n <= 0) return n <= 0 ? SE3ICP_ERR_EMPTY_CLOUD : SE3ICP_ERR_INVALID_ARG;
-    if (k <= 0) return SE3ICP_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(dev_));
-    npairs_ = 0;
-    int rc = alloc_points(n, k);
-    if (rc) return rc;
-    std::vector<CloudReq> cl(1);
-    cl[0].in = xyz;
-    cl[0].n = n;
-    cl[0].st.k_knn = k;
-    cl[0].st.k_lrf = k;
-    cl[0].st.alpha = 1.0;
-    cl[0].st.beta = 1.0;
-    cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
+    const int rc = setup_single(xyz, frames, n, k, true, false);
     if (rc) return rc;
     std::vector<double> fr(12 * (size_t)ld_);
     HIPCHK(hipMemcpyAsync(fr.data(), d_fr64_.p, sizeof(double) * 12 * ld_, hipMemcpyDeviceToHost, stream_));
@@ -2148,20 +2034,7 @@ int Engine::toldi_frames(const double* xyz, int64_t n, int k, double* frames) {
 }
 
 int Engine::estimate_normals(const double* xyz, int64_t n, int k, double* normals) {
-    if (!ok_) return SE3ICP_ERR_NO_DEVICE;
-    if (!xyz || !normals || n <= 0) return n <= 0 ? SE3ICP_ERR_EMPTY_CLOUD : SE3ICP_ERR_INVALID_ARG;
-    if (k <= 0) return SE3ICP_ERR_INVALID_ARG;
-    HIPCHK(hipSetDevice(dev_));
-    npairs_ = 0;
-    int rc = alloc_points(n, k);
-    if (rc) return rc;
-    std::vector<CloudReq> cl(1);
-    cl[0].in = xyz;
-    cl[0].n = n;
-    cl[0].st.k_knn = k;
-    cl[0].st.k_nrm = k;
-    cl[0].st.norm_scale = 1.0;
-    rc = setup_clouds(cl, false, false, false, 1.0, stream_);
+    const int rc = setup_single(xyz, normals, n, k, false, true);
     if (rc) return rc;
     std::vector<double> nr(3 * (size_t)ld_);
     HIPCHK(hipMemcpyAsync(nr.data(), d_nrm64_.p, sizeof(double) * 3 * ld_, hipMemcpyDeviceToHost, stream_));

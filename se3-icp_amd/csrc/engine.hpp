@@ -187,6 +187,8 @@ class Engine {
             : perm(o), pos(o), vec(o), vec64(o), vec64a(o), blo(o), bhi(o), lo(o), hi(o), scr(o), vecT(o) {}
     };
     int init();
+    // the front of knn_self (neither), toldi_frames and estimate_normals: checks, one cloud's setup
+    int setup_single(const double* xyz, const void* out, int64_t n, int k, bool frames, bool normals);
     template <class T>
     T* ensure(DevBuf& b, size_t count);
     int alloc_points(int64_t ntot, int kmax, bool knn_list = false);
@@ -210,18 +212,21 @@ class Engine {
     // stream, the kernel times' reset and the begin event.  The entry's own argument checks
     // surround the trace's: `args` is the status of those before it, `rest` (evaluated by the
     // entry only when `args` is 0) of those after it.
-    // The armed setup record (se3icp_set_setup_record) rides beside the trace: taken and validated
-    // with it, sr_pair the recorded pair's index among the pairs run_pairs is given (a sweep
-    // remaps it per group as it does the trace's).
+    // The armed setup record (se3icp_set_setup_record) and tree record (se3icp_set_tree_record)
+    // ride beside the trace: taken and validated with it, in that order; sr_pair / tk_pair the
+    // recorded pair's index among the pairs run_pairs is given (the trace carries its own).
     struct Call {
-        se3icp_trace* tr = nullptr;
         hipStream_t s = nullptr;
+        se3icp_trace* tr = nullptr;
         se3icp_setup_record* sr = nullptr;
-        int sr_pair = -1;
-        se3icp_tree_record* tr_rec = nullptr;  // the armed tree record, taken and remapped as sr is
-        int tr_pair = -1;
+        se3icp_tree_record* tk = nullptr;
+        int sr_pair = -1, tk_pair = -1;
     };
     int open_call(int args, int64_t nslots, int rest, hipStream_t user_stream, Call* c);
+    // The Call of a sweep group of g variants from v0 over P pairs: the records of `c` whose pair
+    // (result index v * P + p) lies in the group, remapped to the group's pairs.  The trace is
+    // remapped in a copy, *gtr; the caller writes its iters_recorded back.
+    static Call group_call(const Call& c, int v0, int g, int P, se3icp_trace* gtr);
     // The clouds back to back in the SoA columns: offsets, chunk list, inputs (uploaded, or
     // pointed at when on_device) and the cloud, setup, chunk and input tables on the device.
     int upload_clouds(const std::vector<CloudReq>& clouds, bool on_device, hipStream_t s);
@@ -233,8 +238,14 @@ class Engine {
     // reference's preprocessing, the centers and scale[p] staying on the device.
     int setup_clouds(const std::vector<CloudReq>& clouds, bool on_device, bool pairs, bool normalize, double scale_pre,
                      hipStream_t s);
-    // kNN / frames / normals of the clouds set up so far (step 4 of setup_clouds)
-    int setup_knn(hipStream_t s);
+    // The front of setup_clouds and setup_pairs_shared behind upload_clouds: k_ingest, then the
+    // normalization parameters -- normalize: centers, radius and scales on the device, no host
+    // wait; otherwise the centroids on the host (one wait) and the setup table's copy.  The
+    // caller queues launch_normalize behind it.
+    int queue_norm_params(bool pairs, bool normalize, double scale_pre, hipStream_t s);
+    // kNN / frames / normals of the clouds set up so far (step 4 of setup_clouds).  sel: the
+    // plan of a selection that seeds or takes (select_by_class); null: a plain selection.
+    int setup_knn(hipStream_t s, const SelectPlan* sel = nullptr);
     // setup_clouds for the 2P resident cloud slots of a device batch that may hold one cloud
     // several times (graph.hpp): the slots are ingested, normalized and given their 3-D trees
     // in place exactly as setup_clouds does, hashed on the way, and compared where the hashes
@@ -258,8 +269,8 @@ class Engine {
     // results and, with `ropts` and `reports`, the report of every pair).  Pair q takes its
     // parameters from vprm[q / pairs_per_variant] (a plain batch: one variant of npairs pairs;
     // a sweep group: the group's variants, pair q a replica of base pair
-    // q % pairs_per_variant).  sweep: the setup time is the shared setup's (events 12 -> 8)
-    // plus the group's (9 -> 13) instead of 12 -> 13.
+    // q % pairs_per_variant).  sweep: the setup time is the shared setup's (call begin -> shared
+    // done) plus the group's (group begin -> setup done) instead of call begin -> setup done.
     int run_pairs(const MethodPlan& mp, int npairs, const int64_t* ns, const int64_t* nt,
                   const se3icp_params* vprm, int pairs_per_variant, bool sweep, const Call& c, se3icp_result* out,
                   const se3icp_report_options* ropts, se3icp_report* reports);
@@ -355,35 +366,23 @@ class Engine {
     // conf64 between the call's two layouts), the segment and chunk tables of the k_graph kernels
     DevBuf g_raw_xyz_{bufs_}, g_raw_conf_{bufs_}, g_seg_{bufs_}, g_chunks_{bufs_};
     // setup_pairs_shared: the slots' hashes, the compare table and its flags, their host copies
-    // and the host copy of the device's setup table
+    // and the device's setup table on the host
     DevBuf d_share_hash_{bufs_}, d_share_pairs_{bufs_}, d_share_same_{bufs_};
     Pinned<uint64_t> h_share_hash_{pins_};
     Pinned<int32_t> h_share_same_{pins_};
     Pinned<CloudSetup> h_share_setup_{pins_};
     std::vector<SharePair> share_pairs_;
-    std::vector<CloudSetup> share_setup_;
-    // select_by_class: the uses' own setup table, the selection's, the chunks and segments of
-    // k_graph_share (host side of copies that run until the call's last synchronisation)
-    std::vector<CloudSetup> sel_batch_, sel_run_;
-    std::vector<ChunkWork> sel_chunks_;
-    std::vector<GraphSeg> sel_seg_;
+    // select_by_class: the call's selection plan (graph.hpp), handed to setup_knn and never read as
+    // state; kept because queued copies read its arrays until the call's last synchronisation
+    SelectPlan sel_;
     int64_t graph_stats_[9] = {};
-    // select_by_class -> setup_knn: whether this selection seeds, where each use stores / reads
-    // seeds, the floats of the seed buffer, and the buffers on the device
-    bool seed_on_ = false;
-    std::vector<SeedRef> seed_ref_;
-    int64_t seed_floats_ = 0;
+    // the seeds, and where each use stores / reads them, on the device
     DevBuf d_seed_{bufs_}, d_seed_ref_{bufs_};
     int64_t seed_stats_[4] = {};
     // se3icp_set_lrf_taking: 0 a seeded class with its source's tree order takes the source's
     // neighbour lists (default), 1 off, 2 a diagnostic: every stored bound halved, every wave redone
     int lrf_taking_ = 0;
-    // select_by_class -> setup_knn: whether this selection takes, bit 0 (stores lists) / bit 1
-    // (takes) of every use, the entries per list, and the lists, flags and redo mask on the device
-    // (the bounds Lb follow the seeds in d_seed_)
-    bool take_on_ = false;
-    std::vector<int32_t> take_flag_;
-    int take_stride_ = 0;
+    // the lists, the uses' take flags and the redo mask on the device (the bounds Lb follow the seeds)
     DevBuf d_take_lists_{bufs_}, d_take_flag_{bufs_}, d_take_mask_{bufs_};
     int64_t take_stats_[TS_COUNT] = {};
     // graph_plan_trees of the call: per slot -1 or the slot whose tree order it adopts.  Set by
@@ -429,10 +428,12 @@ class Engine {
     Pinned<unsigned long long> h_lrf_stats_{pins_};   // k_lrf work counters (read at the next sync)
     Pinned<unsigned long long> h_loop_stats_{pins_};  // loop NN work counters (pinned: an async copy, not a staged one)
     bool lrf_stats_pending_ = false;
-    // 6/7: k_lrf time; 12/13/14: batch begin / setup done / loop done (GPU-timeline phase
-    // times); 8/9: a sweep's shared setup done / group begin; 10/11: setup_pairs_shared's hashes
-    // and compare flags on the host; 15: sync_stream; the rest unused
-    hipEvent_t ev_[16];
+    // k_lrf time; a sweep's shared setup done / group begin; setup_pairs_shared's hashes and
+    // compare flags on the host; call begin / setup done / loop done (GPU-timeline phase times);
+    // sync_stream
+    enum Ev : int { EV_LRF_BEGIN, EV_LRF_END, EV_SHARED_DONE, EV_GROUP_BEGIN, EV_SHARE_HASH, EV_SHARE_FLAGS,
+                    EV_CALL_BEGIN, EV_SETUP_DONE, EV_LOOP_DONE, EV_SYNC, EV_COUNT };
+    hipEvent_t ev_[EV_COUNT];
     // loop iterations in flight: kernel-time events and launched NN phases per ring slot
     static constexpr int kLoopRing = 4, kLoopEv = 7;
     hipEvent_t loop_ev_[kLoopRing * kLoopEv];

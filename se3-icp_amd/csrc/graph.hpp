@@ -18,11 +18,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <map>
 #include <utility>
 #include <vector>
+
+#include "view.hpp"
 
 namespace se3icp {
 
@@ -156,33 +159,16 @@ struct SeedClass {
 // its f32 copy uncentred (as the source has) and asks for no more neighbours, Kw = min(k_knn, n),
 // than the source found.  Nothing is seeded without the normalization or with a class per use
 // (sharing level 1).  Returns the seeded classes.
+inline int32_t graph_plan_seeds_posed(const GraphPlan& plan, const int32_t* k_knn, const int64_t* n_pts,
+                                      const int32_t* raw, const int32_t* rigid, bool cross,
+                                      std::vector<SeedClass>* seed, int32_t* n_cross);
 inline int32_t graph_plan_seeds(const GraphPlan& plan, const int32_t* k_knn, const int64_t* n_pts,
                                 std::vector<SeedClass>* seed) {
-    const int32_t K = (int32_t)plan.classes.size();
-    seed->assign((size_t)K, SeedClass{-1, 1.0});
-    if (!plan.normalize || !plan.dedupe) return 0;
-    auto uncentred = [](const GraphClass& g) { return g.f32_center[0] == 0.0 && g.f32_center[1] == 0.0 && g.f32_center[2] == 0.0; };
-    std::map<int32_t, int32_t> source;  // cloud -> its first class that selects
-    int32_t seeded = 0;
-    for (int32_t k = 0; k < K; ++k) {
-        if (k_knn[k] <= 0) continue;
-        const GraphClass& g = plan.classes[k];
-        auto it = source.find(g.cloud);
-        if (it == source.end()) {
-            source[g.cloud] = k;
-            continue;
-        }
-        const int32_t a = it->second;
-        const GraphClass& ga = plan.classes[a];
-        const int64_t kw = k_knn[k] < n_pts[k] ? k_knn[k] : n_pts[k], kwa = k_knn[a] < n_pts[a] ? k_knn[a] : n_pts[a];
-        const double rho = g.norm_scale / ga.norm_scale;
-        if (std::memcmp(g.norm_center, ga.norm_center, sizeof(g.norm_center)) != 0 || !uncentred(g) || !uncentred(ga) ||
-            n_pts[k] != n_pts[a] || kw > kwa || !(rho > 0.0) || !std::isfinite(rho * rho))
-            continue;
-        (*seed)[k] = SeedClass{a, rho * rho};
-        ++seeded;
-    }
-    return seeded;
+    int32_t nv = 0;  // every cloud its own, unposed, variant (graph_plan_seeds_posed)
+    for (const GraphClass& g : plan.classes) nv = std::max(nv, g.cloud + 1);
+    std::vector<int32_t> raw((size_t)nv), rigid((size_t)nv, 1);
+    for (int32_t v = 0; v < nv; ++v) raw[v] = v;
+    return graph_plan_seeds_posed(plan, k_knn, n_pts, raw.data(), rigid.data(), true, seed, nullptr);
 }
 
 // ---- taking the source's neighbour lists
@@ -454,13 +440,152 @@ inline int graph_check(int32_t n_clouds, const int64_t* n_pts, const int64_t* of
     return 0;
 }
 
-// ---- k_graph.hip
-struct View;
-struct ChunkWork;
 // Per destination cloud.  k_graph_normalize: src_off is the cloud's first slot among the raw
 // columns.  k_graph_share: src_off / src_cloud are the first slot and the cloud whose SE(3)
 // rows it takes (frames != 0), nrm_off the first slot of its normals (its own: none copied).
 struct GraphSeg { int32_t src_off; int32_t src_cloud; int32_t nrm_off; int32_t frames; };
+
+// ---- the neighbour selection of planned uses as a value (Engine::select_by_class, setup_knn)
+// Everything select_by_class decides before it queues anything.  The engine keeps the call's
+// SelectPlan until the call's last synchronisation, because queued copies read its arrays; no
+// code reads it as state.
+struct SelectSwitches {
+    int lrf_seeding, lrf_taking, lrf_exact;  // se3icp_set_lrf_seeding / _taking / _exact
+    bool knn_list;                           // the sorted lists are asked for (se3icp_knn_self)
+    int pose_seeding;                        // se3icp_set_pose_seeding
+};
+struct SelectPlan {
+    std::vector<int32_t> home;      // [classes]: the class's first use, which selects for it
+    // [uses]: the uses' own setup table, and the selection's: k_lrf, k_nrm, k_knn are 0 off a home
+    std::vector<CloudSetup> batch, run;
+    std::vector<GraphSeg> seg;      // [uses]: k_graph_share's table
+    std::vector<ChunkWork> chunks;  // of the uses that take frames or normals from another use
+    bool seeds = false, takes = false;
+    std::vector<SeedRef> seed_ref;  // [uses] when seeds
+    int64_t seed_floats = 0;        // the floats of the seed buffer
+    std::vector<int32_t> take_flag; // [uses] when takes: bit 0 stores lists, bit 1 takes
+    int take_stride = 0;            // entries per list
+    int seed_mode = 0, take_mode = 0;  // the switches' lrf_seeding / lrf_taking, for k_lrf8
+    // graph_stats[GS_FULL]; with seeds seed_stats[0], init_stats[IS_CROSS_SEEDED]; with takes
+    // take_stats[TS_CLASSES]
+    int64_t full = 0, seeded = 0, cross = 0, taking = 0;
+};
+// clouds, batch [uses]: the uses' layout and setup table; k_lrf: the method's TOLDI k (frames exactly when the plan
+// normalizes); tree_donor: graph_plan_trees' table if a slot adopted, else empty; pose_raw /
+// pose_rigid: per variant (graph_plan_seeds_posed), empty in a call without a posed edge.
+inline SelectPlan graph_plan_selection(const GraphPlan& plan, const CloudDev* clouds, const CloudSetup* batch,
+                                       int32_t k_lrf, const SelectSwitches& sw, const std::vector<int32_t>& tree_donor,
+                                       const std::vector<int32_t>& pose_raw, const std::vector<int32_t>& pose_rigid) {
+    const int32_t U = (int32_t)plan.use_class.size(), K = (int32_t)plan.classes.size();
+    const bool se3 = plan.normalize;
+    SelectPlan sp;
+    sp.seed_mode = sw.lrf_seeding;
+    sp.take_mode = sw.lrf_taking;
+    sp.home.assign((size_t)K, -1);
+    for (int32_t u = 0; u < U; ++u)
+        if (sp.home[plan.use_class[u]] < 0) sp.home[plan.use_class[u]] = u;
+    sp.batch.assign(batch, batch + U);
+    sp.run = sp.batch;
+    sp.seg.assign((size_t)U, GraphSeg{});
+    for (int32_t u = 0; u < U; ++u) {
+        const int32_t k = plan.use_class[u];
+        const GraphClass& gc = plan.classes[k];
+        // a home use selects for its class (the largest normals k of the class's uses; none
+        // where another class of the cloud owns the normals), the others select nothing
+        CloudSetup& st = sp.run[u];
+        const bool is_home = sp.home[k] == u;
+        st.k_lrf = is_home ? k_lrf : 0;
+        st.k_nrm = (is_home && gc.nrm_from == k) ? gc.k_nrm : 0;
+        st.k_knn = std::max(st.k_lrf, st.k_nrm);
+        sp.full += st.k_knn > 0;
+        const int32_t hf = sp.home[k], hn = sp.home[gc.nrm_from];  // where its frames / normals are computed
+        sp.seg[u] = GraphSeg{clouds[hf].off, hf, clouds[hn].off, (hf != u && se3) ? 1 : 0};
+        if ((hf != u && se3) || hn != u)
+            for (int64_t p0 = 0; p0 < clouds[u].n; p0 += kChunk) sp.chunks.push_back(ChunkWork{u, (int32_t)p0});
+    }
+    // seeding: a cloud's later classes start from its first class's neighbour distances
+    // (graph_plan_seeds; k_lrf8 only, so not under se3icp_set_lrf_exact)
+    if (sw.lrf_seeding == 1 || sw.lrf_exact != 0 || sw.knn_list) return sp;
+    std::vector<int32_t> kk((size_t)K);
+    std::vector<int64_t> nn((size_t)K);
+    for (int32_t k = 0; k < K; ++k) {
+        kk[k] = sp.run[sp.home[k]].k_knn;
+        nn[k] = clouds[sp.home[k]].n;
+    }
+    std::vector<SeedClass> sc;
+    int32_t cross = 0;
+    const int32_t seeded = pose_raw.empty() ? graph_plan_seeds(plan, kk.data(), nn.data(), &sc)
+                                            : graph_plan_seeds_posed(plan, kk.data(), nn.data(), pose_raw.data(),
+                                                                     pose_rigid.data(), sw.pose_seeding == 0, &sc, &cross);
+    int64_t total = 0;
+    for (int32_t k = 0; k < K; ++k)
+        if (sc[k].from >= 0) total += nn[k];  // (an upper bound of the buffer: a source may seed several)
+    if (seeded <= 0 || total > INT32_MAX) return sp;
+    sp.seed_ref.assign((size_t)U, SeedRef{-1, -1, 1.0});
+    for (int32_t k = 0; k < K; ++k) {
+        if (sc[k].from < 0) continue;
+        SeedRef& src = sp.seed_ref[sp.home[sc[k].from]];
+        if (src.store < 0) {
+            src.store = (int32_t)sp.seed_floats;
+            sp.seed_floats += nn[k];
+        }
+        sp.seed_ref[sp.home[k]].load = src.store;
+        sp.seed_ref[sp.home[k]].rho2 = sc[k].rho2;
+    }
+    sp.seeded = seeded;
+    sp.cross = cross;
+    sp.seeds = true;
+    // taking: a seeded class with its source's tree order takes the source's lists
+    // (graph_plan_takes); only with both switches at their defaults (taking mode 2 is the
+    // default with every bound halved)
+    if (sw.lrf_seeding != 0 || sw.lrf_taking == 1 || (int32_t)tree_donor.size() != U) return sp;
+    std::vector<uint8_t> tk;
+    const int32_t taking = graph_plan_takes(plan, sc, kk.data(), nn.data(), sp.home.data(), tree_donor, &tk);
+    int64_t kw_max = 0;
+    for (int32_t k = 0; k < K; ++k)
+        if (tk[k]) kw_max = std::max<int64_t>(kw_max, std::min<int64_t>(kk[k], nn[k]));
+    if (taking <= 0 || 2 * sp.seed_floats > INT32_MAX) return sp;
+    sp.take_flag.assign((size_t)U, 0);
+    for (int32_t k = 0; k < K; ++k) {
+        if (!tk[k]) continue;
+        sp.take_flag[sp.home[k]] |= 2;
+        sp.take_flag[sp.home[sc[k].from]] |= 1;
+    }
+    // (lists of Kw <= 128 entries, 16-B aligned; longer ones are never taken)
+    sp.take_stride = (int)((std::min<int64_t>(kw_max, kSmallK) + 3) & ~(int64_t)3);
+    sp.taking = taking;
+    sp.takes = true;
+    return sp;
+}
+
+// The three wave tables of k_lrf8 over the clouds of a selection, eight queries per wave and
+// waves aligned to each cloud's first point: wb[t * (nclouds + 1) + c] is cloud c's first wave
+// in table t.  Table 0: the unseeded and the storing clouds; 1: the seeded clouds, in a launch
+// of their own behind the one that stores their seeds; 2: the taking clouds among them, a launch
+// that takes the stored lists and a seeded one over the same table for the waves that could not.
+// A cloud that wants no neighbours gets no waves (the kernel's search for a wave's cloud takes the
+// last one that starts at or before it).  sel null: a plain selection, every wave in table 0.
+struct WaveTables {
+    std::vector<int32_t> wb;  // [3 * (nclouds + 1)]
+    int32_t nw, nw_sd, nw_tk;
+};
+inline WaveTables select_wave_tables(int32_t nclouds, const CloudDev* clouds, const CloudSetup* setup,
+                                     const SelectPlan* sel) {
+    const int32_t nt = nclouds + 1;
+    std::vector<int32_t> wb(3 * (size_t)nt, 0);
+    for (int32_t c = 0; c < nclouds; ++c) {
+        const int32_t waves = setup[c].k_knn > 0 ? (clouds[c].n + 7) / 8 : 0;
+        const bool sd = sel && sel->seeds && sel->seed_ref[c].load >= 0;
+        const bool tk = sd && sel->takes && (sel->take_flag[c] & 2);
+        wb[c + 1] = wb[c] + (sd ? 0 : waves);
+        wb[nt + c + 1] = wb[nt + c] + (sd && !tk ? waves : 0);
+        wb[2 * nt + c + 1] = wb[2 * nt + c] + (tk ? waves : 0);
+    }
+    const int32_t nw = wb[nclouds], nw_sd = wb[nt + nclouds], nw_tk = wb[2 * nt + nclouds];
+    return WaveTables{std::move(wb), nw, nw_sd, nw_tk};
+}
+
+// ---- k_graph.hip
 // k_share_compare: slot's bytes against those of the first slot of its group
 struct SharePair { int32_t slot; int32_t first; };
 // hash[u] += the content hash of cloud slot u's raw input (the caller clears it)
